@@ -23,7 +23,14 @@ broadcast and the unsharded push-pull), so the 1 -> N ratio is explicit.  `value
 delivered sends (friend slots not dropped, :144-145) are 2 % more -- they also
 reach crashed nodes -- and are config.delivered_per_s / delivered_per_step.
 
-Extensions in the same line: config C3 (10,000 trials of N = 1e5, batched
+A plain run (`--gpus G --steps N --warmup W`) does only what the headline needs:
+it builds the overlay, warms up, times the N steps, writes the last step's
+outputs if `--dump-outputs DIR` is given, and prints the line.  Everything
+below -- the extension legs, the roofline's instrumented broadcast, the CPU
+baseline -- runs only with `--full` (the line's `extensions`, `roofline`,
+`cpu_baseline` are null and `strong_scaling` is absent without it).
+
+Extensions in the same line (--full): config C3 (10,000 trials of N = 1e5, batched
 contexts, split over the ranks), config C4 (N = 1e8, fanout 18, fanin 19,
 one broadcast node-range sharded over the ranks: each rank expands its own
 fires and an all-to-all per window inside libgossip_hip.so moves every message
@@ -35,7 +42,11 @@ one GPU (tests/test_bench_ranks.py).
 Roofline: HBM-bound; 12 algorithmic bytes per delivered send (4-B friend id +
 4-B read and 4-B write of the target's state word), divided by
 the device time of the tick kernels measured with HIP events on the engine's
-own stream (an extra, instrumented broadcast after the timed steps).
+own stream (an extra, instrumented broadcast after the timed steps; --full).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as
+DIR/<name>.npy (dump_outputs below); the workload is seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -91,7 +102,18 @@ def parse():
                     help="world > 1: the ranks' exchange -- RCCL inside the library (one GPU per rank), or "
                          "host callbacks over a gloo group (gs_create_rank_exchange; ranks may share a GPU)")
     ap.add_argument("--c4-n", type=int, default=100_000_000, help="nodes of the C4 leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the roofline's instrumented broadcast, "
+                         "the extension legs (C3, C4, push-pull, failure masks, sharded runs) and the CPU "
+                         "baseline; the --no-*, --cpu-*, --c3-*, --c4-n, --pp-shards, --shard-scaling and "
+                         "--ext-deadline options act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy "
+                         "(in the tree: bench_outputs/, which git ignores)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def log(msg):
@@ -248,10 +270,10 @@ def main():
         sim.broadcast_begin(-1)
         polls, status = sim.run(poll=10)
         tot = sim.totals()
-        return tot, status
+        return tot, status, polls
 
     for _ in range(a.warmup):
-        tot, status = one_step()
+        tot, status, _polls = one_step()
         log(f"rank {rank}: warmup ticks={tot['tick']} sent={tot['sent']} status={status}")
 
     def barrier():
@@ -264,7 +286,7 @@ def main():
     sent = counted = 0
     ticks = []
     for _ in range(a.steps):
-        tot, status = one_step()
+        tot, status, polls = one_step()
         sent += tot["sent"]
         counted += tot["messages"]
         ticks.append(tot["tick"])
@@ -282,8 +304,11 @@ def main():
     # the roofline prices) are 2 % more and reported as config.delivered_per_s
     value = counted_all / elapsed
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, sim, polls, tot, status)
+
     roof = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         sim.set_flags(True)
         sim.reset()
         sim.broadcast_begin(-1)
@@ -312,7 +337,7 @@ def main():
                 "broadcast_device_ms": round(kern_ms, 3)}
         sim.set_flags(False)
 
-    ext = None if a.no_extensions else {}
+    ext = {} if a.full and not a.no_extensions else None
     out = Emitter(rank)
     out.line = {
         "metric": "gossip messages delivered/sec (node) at N=1e9; rounds-to-coverage parity",
@@ -354,7 +379,7 @@ def main():
         out.arm(a.ext_deadline, ext)
         ext["flood_failed_1pct"] = guarded("flood_failed_1pct", lambda: flood_failed(a, sim))
     sim.close()
-    if not a.no_extensions:
+    if ext is not None:
         # round 5 put C3 and C4 before push-pull when allocations after ~100 GB
         # of frees ran seconds slow; the library's cache
         # of large device blocks (gs_devmem.cpp) now keeps freed blocks mapped
@@ -381,13 +406,74 @@ def main():
     out.line["devmem"]["process"] = devmem_delta({k: 0 for k in gs.memory_stats()})
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_n > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_n > 0:
         cpu = cpu_baseline(a, gs)
     out.line["cpu_baseline"] = cpu
     gs.trim()  # (see cpu_baseline) every rank gives its cached device blocks back before it exits
     out.emit()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21  # nodes in the seeded sample of the per-node outputs
+DUMP_BLOCK = 4096      # nodes per block of the per-block counts
+DUMP_SEED = 0xD0B5
+
+
+def bitset_views(words, n, ids):
+    """A ceil(n/64)-word bitset (node i = bit i & 63 of word i >> 6) as two
+    float32 arrays: the bits of the nodes `ids`, and the number of set bits in
+    every block of DUMP_BLOCK consecutive nodes (the whole set, 1/DUMP_BLOCK
+    of its size)."""
+    import numpy as np
+    words = np.ascontiguousarray(words, dtype="<u8")
+    bits = ((words[ids >> 6] >> (ids & 63).astype(np.uint64)) & np.uint64(1)).astype(np.float32)
+    pop = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+    per_byte = pop[words.view(np.uint8)]
+    bpb = DUMP_BLOCK // 8
+    blocks = (n + DUMP_BLOCK - 1) // DUMP_BLOCK
+    padded = np.zeros(blocks * bpb, dtype=np.uint8)
+    m = min(per_byte.size, padded.size)
+    padded[:m] = per_byte[:m]
+    return bits, padded.reshape(blocks, bpb).sum(axis=1, dtype=np.uint32).astype(np.float32)
+
+
+def dump_outputs(path, rank, sim, polls, tot, status):
+    """--dump-outputs: what the last timed step (one broadcast: reset,
+    gs_broadcast_begin, gs_run, gs_totals) handed its caller, as
+    <path>/<name>.npy (rank r > 0 of a multi-rank run: <name>_rank<r>.npy):
+
+      poll_stats   float64 [polls, 7]  gs_run's row per 10-tick poll (tick, fired, sent, messages,
+                                       received, crashed, pending; all below 2^53, exact)
+      totals       float64 [7]         gs_totals after the run, the same columns
+      status       float64 [1]         gs_run's status (0 covered, 1 quiescent, 2 max_ticks)
+      sample_nodes float64 [S]         the sampled node ids, ascending: every node when
+                                       n <= DUMP_SAMPLE, else the distinct ids among DUMP_SAMPLE
+                                       draws of a generator seeded with DUMP_SEED (the same in every run)
+      received_sample, crashed_sample      float32 [S]  gs_read_received / gs_read_crashed bits of those nodes
+      received_per_block, crashed_per_block  float32 [ceil(n / DUMP_BLOCK)]  set bits per block of
+                                       DUMP_BLOCK consecutive nodes, over the whole node range
+
+    About 34 MB at N = 1e9.  Runs after the timer stopped."""
+    import numpy as np
+    from gossip_simulator_amd.engine import STAT_FIELDS
+    os.makedirs(path, exist_ok=True)
+    n = sim.n
+    if n <= DUMP_SAMPLE:
+        ids = np.arange(n, dtype=np.int64)
+    else:
+        ids = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    out = {"poll_stats": np.asarray(polls, dtype=np.float64),
+           "totals": np.array([tot[f] for f in STAT_FIELDS], dtype=np.float64),
+           "status": np.array([status], dtype=np.float64),
+           "sample_nodes": ids.astype(np.float64)}
+    for name, words in (("received", sim.received()), ("crashed", sim.crashed())):
+        out[f"{name}_sample"], out[f"{name}_per_block"] = bitset_views(words, n, ids)
+        del words
+    sfx = f"_rank{rank}" if rank else ""
+    for name, arr in out.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), arr)
+    log(f"rank {rank}: wrote {len(out)} arrays ({sum(x.nbytes for x in out.values()) / 1e6:.1f} MB) to {path}")
 
 
 def strong_scaling_block(world, line, ext):

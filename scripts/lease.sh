@@ -5,7 +5,7 @@
 # Usage: bash scripts/lease.sh <tag> <step> [<step> ...]
 #   tests[=pytest args]  the -m gpu suite (or the given targets), scripts/gtest.sh
 #   smoke                __graft_entry__.smoke()
-#   bench[=bench args]   bench.py (default args), the JSON line in bench.json
+#   bench[=bench args]   bench.py --full (every leg), the JSON line in bench.json
 #   pw                   rocprofv3 kernel trace of one broadcast: per-window split (scripts/pw.sh)
 #   prof[=bench args]    rocprofv3 kernel trace of a short bench (scripts/prof.sh)
 #   pmc                  PMC passes over one broadcast (scripts/pmc.sh)
@@ -30,7 +30,7 @@ for step in "$@"; do
       tail -1 "$o/smoke.log" ;;
     bench)
       # shellcheck disable=SC2086
-      timeout -k 10 900 python -u bench.py $arg > "$o/bench.json" 2> "$o/bench.err" || { tail -20 "$o/bench.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full $arg > "$o/bench.json" 2> "$o/bench.err" || { tail -20 "$o/bench.err"; exit 1; }
       cut -c1-400 "$o/bench.json"; grep "\[bench\]" "$o/bench.err" ;;
     pw)
       bash scripts/pw.sh "$tag/pw" > /dev/null || exit 1

@@ -1,7 +1,7 @@
 """bench.py's world > 1 legs, rehearsed on one GPU (verdict r05 item 4).
 
 Two ranks launched the way the driver launches the 8-GPU scaling run
-(`torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2`), with
+(`torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --full`), with
 `--transport gloo`: the ranks share the one GPU and exchange through
 gs_create_rank_exchange's host callbacks instead of RCCL (RCCL refuses two
 ranks on one device).  Every multi-rank leg runs -- the per-rank headline,
@@ -23,7 +23,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--nodes", "2000000", "--c4-n", "2000000", "--c3-trials", "200", "--c3-batch", "100",
+SMALL = ["--full", "--nodes", "2000000", "--c4-n", "2000000", "--c3-trials", "200", "--c3-batch", "100",
          "--steps", "2", "--warmup", "1", "--cpu-n", "0", "--pp-shards", "2", "--ext-deadline", "240"]
 
 
