@@ -258,10 +258,21 @@ hipError_t gs_dev_free(void* p) {
   int sdev = -1;
   {
     std::lock_guard<std::mutex> g(c.mu);
-    auto it = c.ext.find((char*)p);
-    if (it != c.ext.end() && it->second.used) sdev = c.slab[it->second.slab].device;
+    // the extent that holds p, if p lies in a live slab (a trimmed slab's
+    // extents are gone): only its start, while in use, is a block to free.  A
+    // block freed twice (its extent is free, or was merged into a free
+    // neighbour) or an address inside a block must not go on to hipFree: that
+    // would unmap a slab the index still lists
+    auto it = c.ext.upper_bound((char*)p);
+    if (it != c.ext.begin()) {
+      --it;
+      if ((char*)p < it->first + it->second.size) {
+        if (it->first != (char*)p || !it->second.used) return hipErrorInvalidValue;
+        sdev = c.slab[it->second.slab].device;
+      }
+    }
   }
-  if (sdev < 0) {  // not a cached block
+  if (sdev < 0) {  // not the cache's: outside every live slab
     const double t0 = now_ms();
     const hipError_t e = hipFree(p);
     std::lock_guard<std::mutex> g(c.mu);
@@ -329,6 +340,9 @@ size_t gs_devmem_largest() {
   size_t freeb = 0, totalb = 0, best = 0;
   if (hipMemGetInfo(&freeb, &totalb) == hipSuccess && freeb > kMargin) best = freeb - kMargin;
   if (!enabled()) return best;
+  // a cached-size request is rounded up to kGran, and the rounded slab must
+  // fit beside the margin, or gs_dev_malloc trims for it
+  if (best >= kCacheMin) best &= ~(kGran - 1);
   std::lock_guard<std::mutex> g(c.mu);
   auto it = c.freeix.find(dev);
   if (it != c.freeix.end() && !it->second.empty()) best = std::max(best, it->second.rbegin()->first);

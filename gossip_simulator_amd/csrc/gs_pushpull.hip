@@ -30,6 +30,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "gs_internal.h"
+#include "gs_rev_plan.h"
 
 namespace gs {
 namespace {
@@ -1645,48 +1646,23 @@ hipError_t pp_rev_build_part(const DevState& s, unsigned long long* rend, uint32
     }
   }
   const unsigned long long E = cs[nbins];
-  // passes of consecutive bins: forced count, or as many bins as fit the
-  // largest block the allocator can give
-  std::vector<uint32_t> cut{0};
-  {
-    const char* fp = getenv("GS_PP_REV_PASSES");
-    const uint64_t forced = fp ? (uint64_t)std::max(atoi(fp), 1) : 0;
-    if (forced) {
-      const uint64_t per = (nbins + forced - 1) / forced;
-      for (uint64_t c = per; c < nbins; c += per) cut.push_back((uint32_t)c);
-    } else {
-      const uint64_t cap = gs_devmem_largest() / 8;
-      uint64_t acc = 0;
-      for (uint64_t c = 0; c < nbins; ++c) {
-        if (need[c] > cap) return done(hipErrorOutOfMemory);  // not even one bin: the atomic build
-        if (acc + need[c] > cap) {
-          cut.push_back((uint32_t)c);
-          acc = 0;
-        }
-        acc += need[c];
-      }
-    }
-    cut.push_back((uint32_t)nbins);
-  }
+  // passes of consecutive bins (gs_rev_plan.h): a forced count, or as many
+  // bins per pass as fit the largest block the allocator can give
+  const char* fp = getenv("GS_PP_REV_PASSES");
+  const uint64_t forced = fp ? (uint64_t)std::max(atoi(fp), 1) : 0;
+  const RevPlan plan = pp_rev_plan(h.data(), need.data(), nbins, forced ? 0 : gs_devmem_largest() / 8, forced);
+  if (!plan.ok) return done(hipErrorOutOfMemory);  // not even one bin: the atomic build
+  const std::vector<uint32_t>& cut = plan.cut;
   const size_t P = cut.size() - 1;
   if (passes_out) *passes_out = (uint32_t)P;
-  unsigned long long rec_max = 1, frec_max = 1;
-  for (size_t p = 0; p < P; ++p) {
-    unsigned long long r = 0, f = 0;
-    for (uint32_t c = cut[p]; c < cut[p + 1]; ++c) {
-      r += h[c];
-      f += need[c] - h[c];
-    }
-    rec_max = std::max(rec_max, r);
-    frec_max = std::max(frec_max, f);
-  }
-  // one block for both copies: it fits the extent the plan was made for
-  RV(dev_malloc(&tmp, (rec_max + frec_max) * 8));
+  // one block for both copies of the largest pass: it fits the extent the plan
+  // was made for; each pass puts its fine copy right behind its coarse copy
+  RV(dev_malloc(&tmp, plan.tmp_records * 8));
   unsigned long long* rec = tmp;
-  unsigned long long* frec = tmp + rec_max;
   for (size_t p = 0; p < P; ++p) {
     const uint32_t blo = cut[p], bhi = cut[p + 1], nb = bhi - blo;
     const uint64_t fb0 = (uint64_t)blo * 256, fb1 = std::min<uint64_t>((uint64_t)bhi * 256, nbf), nfl = fb1 - fb0;
+    unsigned long long* frec = tmp + plan.rec[p];
     std::vector<unsigned long long> csl(nb + 1, 0), cel(nb, 0), fsl(nfl + 1, 0), ffl(nfl, 0), bbl(nfl, 0);
     std::vector<uint32_t> tpl(nb + 1, 0);
     for (uint32_t c = 0; c < nb; ++c) {
