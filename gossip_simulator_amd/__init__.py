@@ -6,6 +6,7 @@ Layers:
   csrc/gs_broadcast.hip     tick kernels: delivery, infection, crash, stats
   csrc/gs_window.hip        window engine: expand, partition, resolve (default)
   csrc/gs_pushpull.hip      push-pull rounds (extension, config C5)
+  csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI implementation (device state, stream, polling)
   csrc/gs_devmem.cpp        process-wide cache of large device blocks (gs_trim)
@@ -16,7 +17,8 @@ Layers:
 """
 from ._lib import (GS_RUN_COVERED, GS_RUN_MAX_TICKS, GS_RUN_QUIESCENT,  # noqa: F401
                    GossipError, load)
-from .engine import Config, Simulator, covered, memory_stats, trim  # noqa: F401
+from .engine import Config, Simulator, covered, memory_stats, pp_trials_max_n, trim  # noqa: F401
 
-__all__ = ["Config", "Simulator", "GossipError", "covered", "load", "trim", "memory_stats", "GS_RUN_COVERED",
+__all__ = ["Config", "Simulator", "GossipError", "covered", "load", "trim", "memory_stats", "pp_trials_max_n",
+           "GS_RUN_COVERED",
            "GS_RUN_QUIESCENT", "GS_RUN_MAX_TICKS"]

@@ -37,6 +37,7 @@ EXPORTS = (
     "gs_set_flags", "gs_reset", "gs_set_stream", "gs_create_multi", "gs_comm_unique_id",
     "gs_create_rank", "gs_shard_info", "gs_trial_results", "gs_set_trial",
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
+    "gs_pp_trials_max_n",
 )
 
 
@@ -158,6 +159,7 @@ def load():
         "gs_set_trial": ([ctx, C.c_uint32], C.c_int),
         "gs_trim": ([C.c_int, P(sz)], C.c_int),
         "gs_memory_stats": ([P(Timing)], C.c_int),
+        "gs_pp_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -4,8 +4,9 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -device -peers -maxticks) are not echoed in the parameter
-// block, so stdout keeps the reference's shape.
+// (-seed -trial -trials -device -peers -maxticks) are not echoed in the
+// parameter block, so stdout keeps the reference's shape.  -trials T > 1 runs
+// T independent trials in one batched context and prints one line per trial.
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -186,6 +187,8 @@ int main(int argc, char** argv) {
       {"crashrate", "float", "machine crash rate", "0.001", true, "0.001"},
       {"seed", "uint", "Philox key for every random decision", "1", false, "1"},
       {"trial", "uint", "Philox trial index", "0", false, "0"},
+      {"trials", "int", "independent trials trial .. trial+trials-1 batched in one run (one line per trial)",
+       "1", false, "1"},
       {"device", "int", "HIP device ordinal", "0", false, "0"},
       {"gpus", "int", "node-range shards over devices device .. device+gpus-1 (one process)", "1", false,
        "1"},
@@ -227,6 +230,13 @@ int main(int argc, char** argv) {
   }
   p.model = model == "pushpull" ? GS_MODEL_PUSHPULL : GS_MODEL_FLOOD;
   const uint64_t max_ticks = (uint64_t)ival("maxticks");
+  const long long ntrials = ival("trials");
+  if (ntrials < 1 || ntrials > 0x7FFFFFFFll) {
+    fprintf(stderr, "invalid value \"%s\" for flag -trials: want at least 1\n", find("trials")->val.c_str());
+    usage();
+    return 2;
+  }
+  p.trials = (uint32_t)ntrials;
   if (ival("n") <= 0) {
     fprintf(stderr, "panic: invalid argument to Intn\n");  // simulator.go:240 with N=0
     return 2;
@@ -247,6 +257,11 @@ int main(int argc, char** argv) {
   const auto w0 = std::chrono::steady_clock::now();
   const std::string peers = find("peers")->val;
   uint64_t stab = 0;
+  if (!peers.empty() && p.trials > 1) {
+    fprintf(stderr, "%s: -peers holds one table; -trials > 1 builds every trial's overlay\n", g_prog);
+    gs_destroy(c);
+    return 2;
+  }
   if (!peers.empty()) {
     std::vector<uint8_t> deg;
     std::vector<uint32_t> ids;
@@ -279,6 +294,27 @@ int main(int argc, char** argv) {
   int32_t status = GS_RUN_MAX_TICKS;
   rc = gs_run(c, 10, max_ticks, polls.data(), polls.size(), &npoll, &status);
   if (rc) return die(c, rc, "gs_run");
+  if (p.trials > 1) {  // one line per trial: its figures at its own stopping poll (gs_trial_results)
+    std::vector<gs_trial_stats> tr(p.trials);
+    size_t ntr = 0;
+    rc = gs_trial_results(c, tr.data(), tr.size(), &ntr);
+    if (rc) return die(c, rc, "gs_trial_results");
+    uint32_t got99 = 0;
+    for (size_t i = 0; i < ntr && i < tr.size(); ++i) {
+      const float percent = (float)tr[i].received / (float)p.n;
+      char pb[64];
+      gs_format_float32(percent * 100.0f, pb, sizeof(pb));
+      printf("trial %" PRIu64 ": %s%% covered, took %s, Total message %" PRIu64 " Total Crashed %" PRIu64 "\n",
+             tr[i].trial, pb, dur_ms(tr[i].tick).c_str(), tr[i].messages, tr[i].crashed);
+      if (tr[i].status == GS_RUN_COVERED) ++got99;
+    }
+    printf("--- %u of %u trials got 99%% ---\n", got99, p.trials);
+    fflush(stdout);
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
+    fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, %u broadcasts %.3f s\n", ov_wall, p.trials, wall);
+    gs_destroy(c);
+    return got99 == p.trials ? 0 : 3;
+  }
   for (size_t i = 0; i < npoll && i < polls.size(); ++i) {
     const float percent = (float)polls[i].received / (float)p.n;
     char pb[64];

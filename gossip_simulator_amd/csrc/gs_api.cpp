@@ -5,7 +5,8 @@
 // kinds of context sit behind the same calls:
 //   plain    one device, one stream, one trial (window / tick / push-pull engine)
 //   batched  one device, `trials` independent trials laid out at trial << tlog
-//            and run by the window engine at once (config C3)
+//            and run at once (config C3): the flood model by the window engine,
+//            push-pull by the trial-resident kernel (a workgroup per trial)
 //   shard    one node range [lo, hi) of one broadcast (config C4): a member of a
 //            group, or one rank of a multi-process run (RCCL inside)
 //   group    gs_create_multi: shards or trial batches over several devices
@@ -23,6 +24,7 @@
 #include "gossip.h"
 #include "gs_comm.h"
 #include "gs_internal.h"
+#include "gs_ppt_plan.h"
 
 using namespace gs;
 
@@ -109,6 +111,10 @@ struct gs_ctx {
   uint32_t* d_tstat = nullptr;          // [trials][kMaxWindow][kTStatFields]
   uint32_t* h_tstat = nullptr;          // pinned copy
   std::vector<TrialAcc> tacc;
+  // batched push-pull trials (gs_pushpull_trials.hip): a workgroup per trial
+  bool ppt = false;
+  PptState pt{};
+  Buf ppt_chk;                          // the stall check's need bytes [trials] (4-aligned), then live u32 [trials]
   // node-range shard (config C4)
   bool shard = false;
   uint32_t G = 1, rank = 0;
@@ -423,8 +429,9 @@ int check_params(const gs_params* p, std::string& why) {
   }
   if (ring_slots(*p) > 4096) { why = "delayhigh must be <= 4096"; return GS_EINVAL; }
   if (p->model > GS_MODEL_PUSHPULL) { why = "model must be GS_MODEL_FLOOD or GS_MODEL_PUSHPULL"; return GS_EINVAL; }
-  if (p->trials > 1 && p->model != GS_MODEL_FLOOD) {
-    why = "batched trials run the flood model (the reference's)";
+  // batched trials (either model) live at trial << tlog | node in one 31-bit id space
+  if (p->trials > 1 && ((uint64_t)p->trials << std::max<uint32_t>(kFineLog, ceil_log2(p->n))) > 0x7FFFFFFFull) {
+    why = "trials x 2^ceil(log2 n) must be < 2^31 (batch fewer trials per context)";
     return GS_EINVAL;
   }
   return GS_OK;
@@ -435,6 +442,11 @@ void refresh_state(gs_ctx* c) {
   s.deg = c->d_deg;
   s.ids = c->d_ids;
   if (c->win) refresh_window(c);
+  if (c->ppt) {
+    c->pt.deg = c->d_deg;
+    c->pt.ids = c->d_ids;
+    c->pt.stride = s.stride;
+  }
 }
 
 int set_stride(gs_ctx* c, uint32_t stride) {
@@ -597,11 +609,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   c->ntot = c->p.n;
   if (c->trials > 1) {
     c->tlog = std::max<uint32_t>(kFineLog, ceil_log2(c->p.n));
-    c->ntot = (uint64_t)c->trials << c->tlog;
-    if (c->ntot > 0x7FFFFFFFull) {
-      why = "trials x 2^ceil(log2 n) must be < 2^31 (batch fewer trials per context)";
-      return GS_EINVAL;
-    }
+    c->ntot = (uint64_t)c->trials << c->tlog;  // < 2^31 (check_params)
   }
   c->shard = shard;
   c->G = G;
@@ -643,7 +651,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
   c->win = !c->pp && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
-  if ((c->trials > 1 || (shard && !c->pp)) && !c->win) {
+  if (((c->trials > 1 && !c->ppt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
           "fanout/fanin <= 32, no GS_FLAG_TICK_ENGINE, at most 2^30 nodes per context or shard)";
     return GS_EINVAL;
@@ -661,7 +669,8 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // `stats` is per-broadcast state that gs_reset clears.
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const bool tick = !c->win && !c->pp;
-  const size_t b_next = c->pp ? al(s.W * 8) + al(pp_summary_total_words(s.W) * 8) : 0;
+  // (batched push-pull trials build `next` in LDS: no second bitset, no summaries)
+  const size_t b_next = c->pp && !c->ppt ? al(s.W * 8) + al(pp_summary_total_words(s.W) * 8) : 0;
   const size_t b_bits = al(s.W * 8), b_ring = tick ? al((size_t)s.R * s.W * 8) : 0,
                b_cflag = tick ? al((size_t)s.R * s.C * 4) : 0,
                b_clist = tick ? al((size_t)s.R * kShards * s.CS * 4) : 0,
@@ -700,6 +709,23 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   if (c->win) {
     int rc = alloc_window(c);
     if (rc) { why = c->err; return rc; }
+  }
+  if (c->ppt) {  // per-trial counter rows and the stall check's buffers
+    const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
+    const size_t cb = (((size_t)c->trials + 3) & ~(size_t)3) + (size_t)c->trials * 4;
+    if (dev_malloc((void**)&c->d_tstat, tb) != hipSuccess || hipHostMalloc((void**)&c->h_tstat, tb) != hipSuccess ||
+        !grow(c->ppt_chk, cb)) {
+      why = "cannot allocate the per-trial counters";
+      return GS_ENOMEM;
+    }
+    PptState& pt = c->pt;
+    pt.recv = s.recv;
+    pt.tstat = c->d_tstat;
+    pt.n = (uint32_t)c->p.n;
+    pt.trials = c->trials;
+    pt.tlog = c->tlog;
+    pt.kd = s.kd;
+    pt.key = s.key;
   }
   c->tacc.assign(c->trials, TrialAcc{});
   c->async_off = getenv("GS_SYNC_WINDOWS") != nullptr;
@@ -779,7 +805,7 @@ void destroy_one(gs_ctx* c) {
     if (ptr) (void)dev_free(ptr);
   for (Buf* b : {&c->gmap, &c->cmsg, &c->fmsg, &c->tmp, &c->xsend, &c->xrecv, &c->pp_rend, &c->pp_rsrc,
                  &c->pp_rslot, &c->pp_ilist, &c->pp_fmask, &c->pp_scan, &c->pp_ctlb, &c->pp_dset, &c->pp_dcnt, &c->pp_rfail,
-                 &c->pp_rend16})
+                 &c->pp_rend16, &c->ppt_chk})
     if (b->p) (void)dev_free(b->p);
   for (void* ptr : {(void*)c->h_cap, (void*)c->h_misc, (void*)c->h_err, (void*)c->h_stats, (void*)c->h_tstat,
                     (void*)c->h_stage, (void*)c->h_rtab, (void*)c->h_glay})
@@ -793,11 +819,58 @@ void destroy_one(gs_ctx* c) {
   delete c;
 }
 
+// Batched push-pull trials: n is a parameter bounded by what `device` grants
+// one workgroup (gs_ppt_plan.h), so it is validated with the other
+// parameters, before any device state is set up; *pl gets the plan (block 0:
+// not such a context).  Before this combination existed gs_create refused it
+// with GS_EINVAL without looking at the device, and C clients probe that
+// (tests/c/abi_test.c, run where no GPU is visible).  Where the device cannot
+// be asked for its limit the combination still cannot be accepted, and that
+// answer is kept: GS_EINVAL, with a message that says no device was visible.
+// Every other create without a device fails with GS_EDEVICE in ctx_setup.
+int check_ppt_n(const gs_params* p, int device, std::string& why, PptPlan* pl) {
+  *pl = PptPlan{};
+  if (p->trials <= 1 || p->model != GS_MODEL_PUSHPULL) return GS_OK;
+  int ndev = 0;
+  uint64_t lim = 0;
+  const bool asked = hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev &&
+                     ppt_lds_limit(device, &lim) == hipSuccess;
+  if (!asked) {
+    (void)hipGetLastError();
+    why = "batched push-pull trials need n within the device's LDS per workgroup (gs_pp_trials_max_n), and HIP "
+          "device " + std::to_string(device) + " is not visible: n = " + std::to_string(p->n) + " is not accepted";
+    return GS_EINVAL;
+  }
+  const PptPlan plan = ppt_plan(p->n, lim);
+  if (!plan.fits) {
+    why = "batched push-pull trials keep a trial's informed set in one workgroup's LDS: n must be <= " +
+          std::to_string(ppt_max_n(lim)) + " on this device (gs_pp_trials_max_n), not " + std::to_string(p->n);
+    return GS_EINVAL;
+  }
+  if (plan.lds_bytes > 65536 && ppt_prepare(device, (uint32_t)plan.lds_bytes) != hipSuccess) {
+    why = "cannot raise the trial-resident kernel's dynamic LDS limit";
+    return GS_EDEVICE;
+  }
+  *pl = plan;
+  return GS_OK;
+}
+
+// Why this thread's last failed create failed: there is no context to carry
+// it, so gs_last_error(NULL) returns it.
+thread_local std::string g_create_err;
+
 int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out) {
   std::string why;
+  PptPlan pl;
   int rc = check_params(params, why);
+  if (!rc) rc = check_ppt_n(params, device, why, &pl);
   if (!rc) {
     gs_ctx* c = new gs_ctx();
+    if (pl.block) {  // batched push-pull trials: the plan check_ppt_n made for this device
+      c->ppt = true;
+      c->pt.block = pl.block;
+      c->pt.lds_bytes = (uint32_t)pl.lds_bytes;
+    }
     rc = ctx_setup(c, params, device, shard, G, rank, why);
     if (!rc) {
       *out = c;
@@ -806,6 +879,7 @@ int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint
     destroy_one(c);
   }
   fprintf(stderr, "gs_create: %s\n", why.c_str());
+  g_create_err = why;
   return rc;
 }
 
@@ -997,15 +1071,31 @@ const char* gs_strerror(int code) {
   }
 }
 
-const char* gs_last_error(const gs_ctx* c) { return c ? c->err.c_str() : "NULL context"; }
+const char* gs_last_error(const gs_ctx* c) {
+  if (c) return c->err.c_str();
+  return g_create_err.empty() ? "NULL context" : g_create_err.c_str();
+}
+
+int gs_pp_trials_max_n(int device, uint64_t* n_max) {
+  if (!n_max) return GS_EINVAL;
+  *n_max = 0;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GS_EDEVICE;
+  uint64_t lim = 0;
+  if (ppt_lds_limit(device, &lim) != hipSuccess) return GS_EDEVICE;
+  *n_max = ppt_max_n(lim);
+  return GS_OK;
+}
 
 int gs_create(const gs_params* params, gs_ctx** out) {
+  g_create_err.clear();
   if (!out) return GS_EINVAL;
   *out = nullptr;
   return create_one(params, params ? params->device : 0, false, 1, 0, out);
 }
 
 int gs_create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out) {
+  g_create_err.clear();
   if (!out || !params || !devices || ndev < 1) return GS_EINVAL;
   *out = nullptr;
   gs_ctx* g = new gs_ctx();
@@ -1104,6 +1194,7 @@ int gs_comm_unique_id(uint8_t id[GS_COMM_ID_BYTES]) {
 }
 
 int gs_create_rank(const gs_params* params, int device, int nranks, int rank, const uint8_t* id, gs_ctx** out) {
+  g_create_err.clear();
   if (!out || !params || nranks < 1 || rank < 0 || rank >= nranks) return GS_EINVAL;
   *out = nullptr;
   const uint32_t T = std::max<uint32_t>(1, params->trials);
@@ -1142,6 +1233,7 @@ int gs_create_rank(const gs_params* params, int device, int nranks, int rank, co
 
 int gs_create_rank_exchange(const gs_params* params, int device, int nranks, int rank, const gs_exchange* ex,
                             gs_ctx** out) {
+  g_create_err.clear();
   if (!out || !params || !ex || !ex->all_gather || !ex->all_reduce_sum_u64 || nranks < 1 || rank < 0 ||
       rank >= nranks)
     return GS_EINVAL;
@@ -2135,14 +2227,25 @@ int gs_broadcast_begin(gs_ctx* c, int64_t sender) {
   if (sender >= 0 && (uint64_t)sender >= c->p.n) return fail(c, GS_EINVAL, "sender out of range");
   reset_counters(c);
   if (c->group && c->gtrials) {
-    for (gs_ctx* m : c->mem)
+    for (gs_ctx* m : c->mem) {
       if (gs_broadcast_begin(m, sender)) return fail(c, GS_EINVAL, m->err);
+      c->recv += m->recv;  // push-pull: every trial's sender is informed at begin
+    }
     c->pending = c->trials;
     c->begun = true;
     return GS_OK;
   }
   const bool batched = c->trials > 1;
   const uint64_t s = sender >= 0 ? (uint64_t)sender : batched ? ~0ull : keyed_sender(c->group ? c->mem[0] : c);
+  if (c->ppt) {  // batched push-pull: each trial's sender is informed
+    CK(c, hipSetDevice(c->dev));
+    CK(c, ppt_seed(c->pt, (uint32_t)s, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    for (TrialAcc& a : c->tacc) a.recv = 1;
+    c->recv = c->pending = c->trials;
+    c->begun = true;
+    return GS_OK;
+  }
   if (c->pp && (c->group || c->pp_shard)) return pp_shard_begin(c, s);
   if (c->pp) {  // push-pull: the sender is informed (unless failed)
     CK(c, hipSetDevice(c->dev));
@@ -3591,6 +3694,35 @@ void account_trials(gs_ctx* c, uint64_t t0, uint32_t nt) {
   }
 }
 
+// Batched push-pull trials: `ticks` rounds of every trial, at most kMaxWindow
+// per launch (the per-trial counter rows); out[k] = the sum of the trials' rows.
+int ppt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out) {
+  CK(c, hipSetDevice(c->dev));
+  const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
+  uint32_t done = 0;
+  while (done < ticks) {
+    const uint32_t batch = std::min<uint32_t>(ticks - done, kMaxWindow);
+    const uint64_t t0 = c->t + 1;
+    CK(c, ppt_rounds(c->pt, (uint32_t)t0, batch, c->stream));
+    CK(c, hipMemcpyAsync(c->h_tstat, c->d_tstat, tb, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < batch; ++k) {
+      unsigned long long s[kStatFields] = {0};
+      for (uint32_t tr = 0; tr < c->trials; ++tr) {
+        const uint32_t* r = c->h_tstat + ((size_t)tr * kMaxWindow + k) * kTStatFields;
+        s[ST_FIRED] += r[TS_FIRED];
+        s[ST_SENT] += r[TS_SENT];
+        s[ST_MSGS] += (uint64_t)r[TS_SENT] - r[TS_DEAD];
+        s[ST_RECV] += r[TS_RECV];
+      }
+      account_tick(c, t0 + k, s, out ? &out[done + k] : nullptr);
+    }
+    account_trials(c, t0, batch);
+    done += batch;
+  }
+  return GS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3628,6 +3760,7 @@ int gs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out) {
   if (c->pp && (c->group || c->pp_shard)) return pp_shard_step(c, ticks, out);
   if (c->group) return shard_step(c, c->mem, ticks, out);
   if (c->shard) return abort_rank(c, shard_step(c, {c}, ticks, out));
+  if (c->ppt) return ppt_step(c, ticks, out);
   CK(c, hipSetDevice(c->dev));
   if (async_ok(c) && ticks > 0) {  // device-driven windows
     uint32_t stop = 0, k = 0;
@@ -3770,6 +3903,43 @@ int pp_stalled(gs_ctx* c, bool* stalled) {
   return GS_OK;
 }
 
+// Batched push-pull trials after a poll: snaps every running trial that
+// stops here -- covered; or the poll informed nobody new in it (r0: the
+// trials' informed counts before the poll) and no call can change its
+// informed set any more (pp_stalled's rule on the trial's own rows and bits,
+// checked on the device for those trials only); or max_ticks -- and counts
+// the rest.
+int ppt_poll_stops(gs_ctx* c, const std::vector<uint64_t>& r0, uint64_t max_ticks, uint32_t* running) {
+  const uint32_t T = c->trials;
+  std::vector<uint8_t> need(T, 0);
+  uint32_t nneed = 0;
+  for (uint32_t tr = 0; tr < T; ++tr) {
+    TrialAcc& a = c->tacc[tr];
+    if (a.status != GS_RUN_RUNNING) continue;
+    if (covered(a.recv, c->p.n)) snap_trial(c, tr, GS_RUN_COVERED);
+    else if (a.recv == r0[tr]) { need[tr] = 1; ++nneed; }
+  }
+  std::vector<uint32_t> live(T, 0);
+  if (nneed && c->st.kd < 100) {  // (kd >= 100: every call is lost, nothing is live)
+    uint8_t* d_need = (uint8_t*)c->ppt_chk.p;
+    uint32_t* d_live = (uint32_t*)(d_need + (((size_t)T + 3) & ~(size_t)3));
+    CK(c, hipSetDevice(c->dev));
+    CK(c, hipMemcpyAsync(d_need, need.data(), T, hipMemcpyHostToDevice, c->stream));
+    CK(c, hipMemsetAsync(d_live, 0, (size_t)T * 4, c->stream));
+    CK(c, ppt_stalled(c->pt, d_need, d_live, c->stream));
+    CK(c, hipMemcpyAsync(live.data(), d_live, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+  }
+  *running = 0;
+  for (uint32_t tr = 0; tr < T; ++tr) {
+    if (c->tacc[tr].status != GS_RUN_RUNNING) continue;
+    if (need[tr] && !live[tr]) snap_trial(c, tr, GS_RUN_QUIESCENT);
+    else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);
+    else ++*running;
+  }
+  return GS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3856,14 +4026,29 @@ int gs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, siz
       return GS_OK;
     }
   }
+  std::vector<uint64_t> tr0;  // batched push-pull: every trial's informed count before the poll
   for (;;) {
     const uint64_t r0 = c->recv;
+    if (trials && c->ppt) {
+      tr0.resize(c->trials);
+      for (uint32_t tr = 0; tr < c->trials; ++tr) tr0[tr] = c->tacc[tr].recv;
+    }
     // one poll (the first may finish a poll the device-driven windows began)
     RC(gs_step(c, (uint32_t)(poll - (c->t - pbase) % poll), nullptr));
     if (out && k < cap)
       out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, c->crashed, c->pending};
     ++k;
     f0 = c->fired; s0 = c->sent; m0 = c->msgs;
+    if (trials && c->ppt) {  // each trial stops at its own poll, by the one-trial push-pull rule
+      uint32_t running = 0;
+      RC(ppt_poll_stops(c, tr0, max_ticks, &running));
+      if (running == 0) {
+        st = GS_RUN_COVERED;
+        for (const TrialAcc& a : c->tacc) st = std::max(st, a.status);
+        break;
+      }
+      continue;
+    }
     if (trials) {  // each trial stops at its own poll (simulator.go:243-251 per process)
       uint32_t running = 0;
       for (uint32_t tr = 0; tr < c->trials; ++tr) {
@@ -4025,6 +4210,7 @@ int gs_set_trial(gs_ctx* c, uint32_t trial) {
   c->p.trial = trial;
   c->st.key.trial = trial;
   c->ws.key.trial = trial;
+  c->pt.key.trial = trial;
   c->peers = false;  // the overlay of the new trials is still to be built (or loaded)
   reset_counters(c);
   return GS_OK;

@@ -470,6 +470,30 @@ hipError_t pp_count(const unsigned long long* words, uint64_t nwords, unsigned l
 hipError_t pp_or_slices(unsigned long long* dst, const unsigned long long* src, uint32_t nslices, uint64_t words,
                         hipStream_t st);
 
+// Batched push-pull trials (gs_pushpull_trials.hip): one workgroup per trial,
+// the trial's informed set in LDS (plan: gs_ppt_plan.h), up to kMaxWindow
+// rounds per launch.  Nodes at trial << tlog | v as in every batched context.
+struct PptState {
+  const uint8_t* deg;
+  const uint32_t* ids;
+  unsigned long long* recv;  // [(trials << tlog) / 64] informed words
+  uint32_t* tstat;           // [trials][kMaxWindow][kTStatFields] per-round counters of every trial
+  uint32_t n, trials, tlog, stride;
+  uint32_t block, lds_bytes; // PptPlan of n on this device
+  int32_t kd;
+  Key key;
+};
+// Per-workgroup LDS the device grants k_ppt_rounds (bytes).
+hipError_t ppt_lds_limit(int device, uint64_t* limit);
+// Opt k_ppt_rounds in to lds_bytes > 64 KiB of dynamic LDS on `device` (once, at create).
+hipError_t ppt_prepare(int device, uint32_t lds_bytes);
+// Every trial's sender informed: `node`, or (~0u) each trial's keyed sender.
+hipError_t ppt_seed(const PptState& s, uint32_t node, hipStream_t st);
+// Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
+hipError_t ppt_rounds(const PptState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
+// live[trial] = 1 where need[trial] and a call could still inform someone (live zeroed by the caller).
+hipError_t ppt_stalled(const PptState& s, const uint8_t* need, uint32_t* live, hipStream_t st);
+
 // Launchers (gs_broadcast.hip).
 hipError_t launch_tick(const DevState& st, uint32_t tick, int mode, hipStream_t s);
 hipError_t launch_slot_reset(const DevState& st, uint32_t slot, hipStream_t s);

@@ -36,7 +36,7 @@ class Config:
     timing: bool = False
     engine: str = "window"  # "window" (default) or "tick" (per-tick atomic engine)
     model: str = "flood"    # "flood" (the reference) or "pushpull" (extension)
-    trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3)
+    trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3), either model
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
                               # rounds bottom-up once |I| >= 96n/256), "dense" (every round streams the
@@ -110,7 +110,9 @@ class Simulator:
             rc = self.L.gs_create(C.byref(self._p), C.byref(h))
             what = "gs_create"
         if rc != 0:
-            raise GossipError(rc, f"{what} failed: {self.L.gs_strerror(rc).decode()}")
+            why = self.L.gs_last_error(None).decode(errors="replace")  # no context: the create's own reason
+            raise GossipError(rc, f"{what} failed: {self.L.gs_strerror(rc).decode()}" +
+                              (f" ({why})" if why and why != "NULL context" else ""))
         self.h = h
         self.n = cfg.n
         self.trials = max(1, int(cfg.trials))
@@ -339,6 +341,18 @@ def trim(device: int = -1) -> int:
     rc = L.gs_trim(int(device), C.byref(out))
     if rc != 0:
         raise GossipError(rc, "gs_trim failed")
+    return int(out.value)
+
+
+def pp_trials_max_n(device: int = 0) -> int:
+    """Largest n a batched push-pull context (model="pushpull", trials > 1) may
+    have on `device` (gs_pp_trials_max_n): a trial's informed set lives in one
+    workgroup's LDS."""
+    L = _lib.load()
+    out = C.c_uint64(0)
+    rc = L.gs_pp_trials_max_n(int(device), C.byref(out))
+    if rc != 0:
+        raise GossipError(rc, "gs_pp_trials_max_n failed")
     return int(out.value)
 
 

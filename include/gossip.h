@@ -63,7 +63,10 @@ enum {
                               * round per tick; each live node calls one Philox-picked friend,
                               * informed callers push, uninformed callers pull; -droprate loses
                               * calls, -crashrate is unused, gs_set_failed masks nodes
-                              * (oracle/gsoracle.h) */
+                              * (oracle/gsoracle.h).  With trials > 1:
+                              * one workgroup per trial, the trial's informed set in LDS, so
+                              * n <= gs_pp_trials_max_n(); the GS_FLAG_PP_* round modes are
+                              * accepted and ignored (there is one round kind) */
 
 /* simulator.go:11-20 (Parameters) + the additive -seed/-trial knobs. */
 typedef struct gs_params {
@@ -82,6 +85,7 @@ typedef struct gs_params {
   /* Batched independent trials (config C3): trials trial .. trial+trials-1 of n
    * nodes each, run at once (one overlay, one broadcast per trial, keyed by
    * its trial number exactly as a one-trial context).  0 or 1 = one trial.
+   * Both models; trials << max(14, ceil(log2 n)) must be < 2^31.
    * The reference runs one trial per process (simulator.go:207-253). */
   uint32_t trials;
   uint32_t reserved0_;
@@ -223,7 +227,17 @@ int gs_create_rank_exchange(const gs_params* params, int device, int nranks, int
  * an unsharded context is one shard [0, n). */
 int gs_shard_info(const gs_ctx* ctx, uint32_t index, uint32_t* nshards, uint64_t* lo, uint64_t* hi);
 void gs_destroy(gs_ctx* ctx);
+/* ctx == NULL: why the calling thread's last gs_create* failed (a failed create
+ * leaves no context to ask; this is how the limit of a batched push-pull
+ * context reaches the caller); "NULL context" if it gave no reason. */
 const char* gs_last_error(const gs_ctx* ctx);
+/* Largest n a batched push-pull context (trials > 1, GS_MODEL_PUSHPULL) may
+ * have on `device`: a trial's two informed bitsets must fit the LDS the
+ * device grants one workgroup.  gs_create refuses a larger n with GS_EINVAL.
+ * (Where no device is visible gs_create keeps answering GS_EINVAL for
+ * trials > 1 with GS_MODEL_PUSHPULL, as it did before the combination
+ * existed; every other create, and this query, then fail with GS_EDEVICE.) */
+int gs_pp_trials_max_n(int device, uint64_t* n_max);
 
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
