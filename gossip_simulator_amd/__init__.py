@@ -17,8 +17,9 @@ Layers:
 """
 from ._lib import (GS_RUN_COVERED, GS_RUN_MAX_TICKS, GS_RUN_QUIESCENT,  # noqa: F401
                    GossipError, load)
-from .engine import Config, Simulator, covered, memory_stats, pp_trials_max_n, trim  # noqa: F401
+from .engine import (Config, Simulator, covered, memory_stats, pp_trials_max_n,  # noqa: F401
+                     pp_trials_max_n_masked, trim)
 
 __all__ = ["Config", "Simulator", "GossipError", "covered", "load", "trim", "memory_stats", "pp_trials_max_n",
-           "GS_RUN_COVERED",
+           "pp_trials_max_n_masked", "GS_RUN_COVERED",
            "GS_RUN_QUIESCENT", "GS_RUN_MAX_TICKS"]

@@ -37,7 +37,7 @@ EXPORTS = (
     "gs_set_flags", "gs_reset", "gs_set_stream", "gs_create_multi", "gs_comm_unique_id",
     "gs_create_rank", "gs_shard_info", "gs_trial_results", "gs_set_trial",
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
-    "gs_pp_trials_max_n",
+    "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked",
 )
 
 
@@ -160,6 +160,7 @@ def load():
         "gs_trim": ([C.c_int, P(sz)], C.c_int),
         "gs_memory_stats": ([P(Timing)], C.c_int),
         "gs_pp_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
+        "gs_pp_trials_max_n_masked": ([C.c_int, P(C.c_uint64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -38,6 +38,7 @@ struct Buf {
 // One trial's running counters and its stopping snapshot (gs_run's rule).
 struct TrialAcc {
   uint64_t fired = 0, sent = 0, msgs = 0, recv = 0, crash = 0, sched = 0, tick99 = 0;
+  uint64_t start = 1;  // batched flood: the sender's own Broadcast (0: a failed sender, never scheduled)
   int32_t status = GS_RUN_RUNNING;
   gs_trial_stats snap{};
 };
@@ -828,13 +829,38 @@ void destroy_one(gs_ctx* c) {
 // be asked for its limit the combination still cannot be accepted, and that
 // answer is kept: GS_EINVAL, with a message that says no device was visible.
 // Every other create without a device fails with GS_EDEVICE in ctx_setup.
+// ppt_lds_limit with its failure in words ("" on success): the HIP call that
+// failed and the runtime's error string.
+std::string ppt_limit_error(int device, bool masked, uint64_t* lim) {
+  const char* where = "";
+  const hipError_t e = ppt_lds_limit(device, masked, lim, &where);
+  if (e == hipSuccess) return std::string();
+  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
+         std::to_string((int)e) + ")";
+}
+
+// A batched push-pull context about to take failure masks: the masked LDS
+// plan of its n on its device.  GS_EINVAL with the limit in `why` where n is
+// past it; nothing of the context is changed.
+int ppt_masked_plan(const gs_ctx* c, PptPlan* plan, std::string& why) {
+  uint64_t lim = 0;
+  why = ppt_limit_error(c->dev, true, &lim);
+  if (!why.empty()) return GS_EDEVICE;
+  *plan = ppt_plan_masked(c->p.n, lim);
+  if (plan->fits) return GS_OK;
+  why = "batched push-pull trials with failure masks keep a third bitset in one workgroup's LDS: n must be <= " +
+        std::to_string(ppt_max_n_masked(lim)) + " on device " + std::to_string(c->dev) +
+        " (gs_pp_trials_max_n_masked), not " + std::to_string(c->p.n);
+  return GS_EINVAL;
+}
+
 int check_ppt_n(const gs_params* p, int device, std::string& why, PptPlan* pl) {
   *pl = PptPlan{};
   if (p->trials <= 1 || p->model != GS_MODEL_PUSHPULL) return GS_OK;
   int ndev = 0;
   uint64_t lim = 0;
   const bool asked = hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev &&
-                     ppt_lds_limit(device, &lim) == hipSuccess;
+                     ppt_lds_limit(device, false, &lim) == hipSuccess;
   if (!asked) {
     (void)hipGetLastError();
     why = "batched push-pull trials need n within the device's LDS per workgroup (gs_pp_trials_max_n), and HIP "
@@ -847,7 +873,7 @@ int check_ppt_n(const gs_params* p, int device, std::string& why, PptPlan* pl) {
           std::to_string(ppt_max_n(lim)) + " on this device (gs_pp_trials_max_n), not " + std::to_string(p->n);
     return GS_EINVAL;
   }
-  if (plan.lds_bytes > 65536 && ppt_prepare(device, (uint32_t)plan.lds_bytes) != hipSuccess) {
+  if (plan.lds_bytes > 65536 && ppt_prepare(device, false, (uint32_t)plan.lds_bytes) != hipSuccess) {
     why = "cannot raise the trial-resident kernel's dynamic LDS limit";
     return GS_EDEVICE;
   }
@@ -1076,16 +1102,37 @@ const char* gs_last_error(const gs_ctx* c) {
   return g_create_err.empty() ? "NULL context" : g_create_err.c_str();
 }
 
-int gs_pp_trials_max_n(int device, uint64_t* n_max) {
+// The limit queries have no context either: a HIP failure is reported like a
+// failed create's reason, through gs_last_error(NULL) and on stderr, with the
+// call that failed and the runtime's error.
+static int pp_trials_limit(int device, bool masked, uint64_t* n_max) {
+  g_create_err.clear();
   if (!n_max) return GS_EINVAL;
   *n_max = 0;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GS_EDEVICE;
-  uint64_t lim = 0;
-  if (ppt_lds_limit(device, &lim) != hipSuccess) return GS_EDEVICE;
-  *n_max = ppt_max_n(lim);
-  return GS_OK;
+  std::string why;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess) {
+    why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
+  } else if (device < 0 || device >= ndev) {
+    why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
+  } else {
+    uint64_t lim = 0;
+    why = ppt_limit_error(device, masked, &lim);
+    if (why.empty()) {
+      *n_max = masked ? ppt_max_n_masked(lim) : ppt_max_n(lim);
+      return GS_OK;
+    }
+  }
+  (void)hipGetLastError();
+  fprintf(stderr, "%s: %s\n", masked ? "gs_pp_trials_max_n_masked" : "gs_pp_trials_max_n", why.c_str());
+  g_create_err = why;
+  return GS_EDEVICE;
 }
+
+int gs_pp_trials_max_n(int device, uint64_t* n_max) { return pp_trials_limit(device, false, n_max); }
+
+int gs_pp_trials_max_n_masked(int device, uint64_t* n_max) { return pp_trials_limit(device, true, n_max); }
 
 int gs_create(const gs_params* params, gs_ctx** out) {
   g_create_err.clear();
@@ -1629,7 +1676,56 @@ int gs_build_overlay(gs_ctx* c, uint64_t max_ticks, gs_window* win, size_t cap, 
 int gs_set_failed(gs_ctx* c, const uint64_t* words, size_t nwords) {
   if (!c || !words || nwords < (c->p.n + 63) / 64) return fail(c, GS_EINVAL, "mask needs ceil(n/64) words");
   if (c->begun) return fail(c, GS_EINVAL, "failure mask must be set before gs_broadcast_begin");
-  if (c->trials > 1) return fail(c, GS_EINVAL, "failure masks are not supported for batched trials");
+  const uint64_t Wn = (c->p.n + 63) / 64;
+  if (c->trials > 1 && nwords < Wn * c->trials)
+    return fail(c, GS_EINVAL, "batched trials: the mask needs ceil(n/64) words per trial, trial-major");
+  if (c->group && c->gtrials) {  // every member its own trials' masks
+    // devices may grant different LDS: every member's limit is checked before
+    // any member takes a mask, so a refusal leaves the whole context unmasked
+    for (gs_ctx* m : c->mem) {
+      PptPlan plan;
+      std::string why;
+      if (m->ppt)
+        if (int rc = ppt_masked_plan(m, &plan, why)) return fail(c, rc, why);
+    }
+    uint64_t off = 0;
+    for (gs_ctx* m : c->mem) {
+      if (int rc = gs_set_failed(m, words + off * Wn, (size_t)m->trials * Wn)) return fail(c, rc, m->err);
+      off += m->trials;
+    }
+    c->failed = true;
+    return GS_OK;
+  }
+  if (c->trials > 1) {  // trial i's words to its slot of the padded id space (tlog >= 14: whole words)
+    CK(c, hipSetDevice(c->dev));
+    uint32_t lds_masked = 0;
+    if (c->ppt) {  // the masked kernel keeps a third bitset in LDS
+      PptPlan plan;
+      std::string why;
+      if (int rc = ppt_masked_plan(c, &plan, why)) return fail(c, rc, why);
+      if (plan.lds_bytes > 65536) CK(c, ppt_prepare(c->dev, true, (uint32_t)plan.lds_bytes));
+      lds_masked = (uint32_t)plan.lds_bytes;
+    }
+    const uint64_t W = c->st.W;
+    std::vector<uint64_t> w(words, words + Wn * c->trials);
+    if (c->p.n & 63)
+      for (uint32_t t = 0; t < c->trials; ++t) w[(t + 1) * Wn - 1] &= (1ull << (c->p.n & 63)) - 1;
+    if (!c->d_failed && dev_malloc(&c->d_failed, W * 8) != hipSuccess)
+      return fail(c, GS_ENOMEM, "cannot allocate the failure mask");
+    CK(c, hipMemsetAsync(c->d_failed, 0, W * 8, c->stream));
+    CK(c, hipMemcpy2DAsync(c->d_failed, ((size_t)1 << c->tlog) / 8, w.data(), Wn * 8, Wn * 8, c->trials,
+                           hipMemcpyHostToDevice, c->stream));
+    CK(c, hipMemcpyAsync(c->st.crash, c->d_failed, W * 8, hipMemcpyDeviceToDevice, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->failed = true;
+    c->st.check_crashed = 1;
+    ++c->fail_ver;
+    if (c->ppt) {
+      c->pt.crash = c->st.crash;
+      c->pt.lds_masked = lds_masked;
+    }
+    return GS_OK;
+  }
   if (c->group) {
     for (gs_ctx* m : c->mem)
       if (gs_set_failed(m, words, nwords)) return fail(c, GS_EINVAL, m->err);
@@ -1690,14 +1786,30 @@ uint64_t keyed_sender(const gs_ctx* c) {
   return uniform(draw0(c->st.key, K_SENDER, 0, 0, 0), (uint32_t)c->p.n);  // simulator.go:240
 }
 
+// Batched trials after their senders were seeded or scheduled: waits for the
+// stream and sets every trial's TrialAcc::start and *count = the trials that
+// started.  `started` is the flag per trial the kernel wrote (the first words
+// of d_tstat, free between broadcasts), or null without failure masks: all did.
+int read_started(gs_ctx* c, const uint32_t* started, uint32_t* count) {
+  if (started) CK(c, hipMemcpyAsync(c->h_tstat, started, (size_t)c->trials * 4, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  *count = 0;
+  for (uint32_t t = 0; t < c->trials; ++t) {
+    c->tacc[t].start = started ? c->h_tstat[t] : 1;
+    *count += (uint32_t)c->tacc[t].start;
+  }
+  return GS_OK;
+}
+
 // Schedules the global sender s if c owns it (and it is live); *sched = 1 if so.
 int begin_one(gs_ctx* c, uint64_t s, uint32_t* sched) {
   *sched = 0;
   CK(c, hipSetDevice(c->dev));
   if (c->trials > 1) {  // every trial's sender (:240 per trial when s == ~0)
-    CK(c, win_schedule(c->ws, (uint32_t)s, 0, c->trials, (uint32_t)c->p.n, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    *sched = c->trials;
+    // per-trial failure masks: a trial whose sender is failed schedules nothing
+    uint32_t* started = c->failed ? c->d_tstat : nullptr;
+    CK(c, win_schedule(c->ws, (uint32_t)s, 0, c->trials, (uint32_t)c->p.n, c->stream, started));
+    RC(read_started(c, started, sched));
     return GS_OK;
   }
   if (s < c->lo || s >= (c->shard ? c->hi : c->p.n)) return GS_OK;  // another shard's node
@@ -2229,20 +2341,22 @@ int gs_broadcast_begin(gs_ctx* c, int64_t sender) {
   if (c->group && c->gtrials) {
     for (gs_ctx* m : c->mem) {
       if (gs_broadcast_begin(m, sender)) return fail(c, GS_EINVAL, m->err);
-      c->recv += m->recv;  // push-pull: every trial's sender is informed at begin
+      c->recv += m->recv;  // push-pull: every trial's live sender is informed at begin
+      c->pending += m->pending;  // the trials that began (all, unless a mask fails a sender)
     }
-    c->pending = c->trials;
     c->begun = true;
     return GS_OK;
   }
   const bool batched = c->trials > 1;
   const uint64_t s = sender >= 0 ? (uint64_t)sender : batched ? ~0ull : keyed_sender(c->group ? c->mem[0] : c);
-  if (c->ppt) {  // batched push-pull: each trial's sender is informed
+  if (c->ppt) {  // batched push-pull: each trial's sender is informed (unless its mask fails it)
     CK(c, hipSetDevice(c->dev));
-    CK(c, ppt_seed(c->pt, (uint32_t)s, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (TrialAcc& a : c->tacc) a.recv = 1;
-    c->recv = c->pending = c->trials;
+    uint32_t* started = c->failed ? c->d_tstat : nullptr;
+    uint32_t k = 0;
+    CK(c, ppt_seed(c->pt, (uint32_t)s, started, c->stream));
+    RC(read_started(c, started, &k));
+    for (TrialAcc& a : c->tacc) a.recv = a.start;
+    c->recv = c->pending = k;
     c->begun = true;
     return GS_OK;
   }
@@ -4054,7 +4168,7 @@ int gs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, siz
       for (uint32_t tr = 0; tr < c->trials; ++tr) {
         TrialAcc& a = c->tacc[tr];
         if (a.status != GS_RUN_RUNNING) continue;
-        const uint64_t pend = 1 + a.sched - a.fired;
+        const uint64_t pend = a.start + a.sched - a.fired;
         if (covered(a.recv, c->p.n)) snap_trial(c, tr, GS_RUN_COVERED);
         else if (pend == 0) snap_trial(c, tr, GS_RUN_QUIESCENT);
         else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);

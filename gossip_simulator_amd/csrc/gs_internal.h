@@ -315,8 +315,10 @@ hipError_t win_close_dd(const WinState& w, const unsigned long long* const* wsta
 // regions with poff[r] = ~0 stay where they are.
 hipError_t win_pack(const WinState& w, const unsigned long long* poff, uint32_t nreg, uint32_t* out, hipStream_t s);
 // Schedule local node `node` (batched: in every trial; ~0u: each trial's keyed sender) at `tick`.
+// started (batched trials with failure masks; else null): a trial whose sender's
+// crash bit is set is not scheduled, and started[trial] = 1 for those that were.
 hipError_t win_schedule(const WinState& w, uint32_t node, uint32_t tick, uint32_t trials, uint32_t n,
-                        hipStream_t s);
+                        hipStream_t s, uint32_t* started = nullptr);
 
 // Push-pull extension (gs_pushpull.hip): one round per tick; `next` is the
 // informed set being built (equal to recv at the start of every round).
@@ -477,18 +479,24 @@ struct PptState {
   const uint8_t* deg;
   const uint32_t* ids;
   unsigned long long* recv;  // [(trials << tlog) / 64] informed words
+  // per-trial failure masks, laid out like recv (null: none; the rounds then
+  // run the unmasked instantiation)
+  const unsigned long long* crash;
   uint32_t* tstat;           // [trials][kMaxWindow][kTStatFields] per-round counters of every trial
   uint32_t n, trials, tlog, stride;
   uint32_t block, lds_bytes; // PptPlan of n on this device
+  uint32_t lds_masked;       // ppt_plan_masked's bytes (0 until a mask is set)
   int32_t kd;
   Key key;
 };
-// Per-workgroup LDS the device grants k_ppt_rounds (bytes).
-hipError_t ppt_lds_limit(int device, uint64_t* limit);
-// Opt k_ppt_rounds in to lds_bytes > 64 KiB of dynamic LDS on `device` (once, at create).
-hipError_t ppt_prepare(int device, uint32_t lds_bytes);
-// Every trial's sender informed: `node`, or (~0u) each trial's keyed sender.
-hipError_t ppt_seed(const PptState& s, uint32_t node, hipStream_t st);
+// Per-workgroup LDS the device grants k_ppt_rounds (bytes), unmasked or masked
+// instantiation.  On an error *where (may be null) names the HIP call that failed.
+hipError_t ppt_lds_limit(int device, bool masked, uint64_t* limit, const char** where = nullptr);
+// Opt that instantiation in to lds_bytes > 64 KiB of dynamic LDS on `device`.
+hipError_t ppt_prepare(int device, bool masked, uint32_t lds_bytes);
+// Every trial's sender informed unless failed: `node`, or (~0u) each trial's
+// keyed sender; started[trial] (may be null) = 1 if it was.
+hipError_t ppt_seed(const PptState& s, uint32_t node, uint32_t* started, hipStream_t st);
 // Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
 hipError_t ppt_rounds(const PptState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
 // live[trial] = 1 where need[trial] and a call could still inform someone (live zeroed by the caller).

@@ -7,6 +7,10 @@
 // 8-byte words, then the block reduction's scratch (four u32 counters per
 // wave of the largest block).  A trial fits when that is within what the
 // device grants one workgroup.
+//
+// With per-trial failure masks (gs_set_failed on a batch) a third, read-only
+// bitset `F` of the trial's failed nodes sits beside them: three bitsets and
+// the same scratch, so the masked limit is two thirds of the unmasked one.
 #ifndef GS_PPT_PLAN_H
 #define GS_PPT_PLAN_H
 
@@ -41,6 +45,21 @@ inline PptPlan ppt_plan(uint64_t n, uint64_t lds_limit_bytes) {
 inline uint64_t ppt_max_n(uint64_t lds_limit_bytes) {
   if (lds_limit_bytes < kPptScratchBytes + 16) return 0;
   return (lds_limit_bytes - kPptScratchBytes) / 16 * 64;
+}
+
+// The masked layout: cur, next and the failed set F, then the scratch.  Same
+// block rule.
+inline PptPlan ppt_plan_masked(uint64_t n, uint64_t lds_limit_bytes) {
+  PptPlan p = ppt_plan(n, lds_limit_bytes);
+  p.lds_bytes = 3 * p.words * 8 + kPptScratchBytes;
+  p.fits = n >= 1 && p.lds_bytes <= lds_limit_bytes;
+  return p;
+}
+
+// The largest n the masked layout fits (0: not even one word does).
+inline uint64_t ppt_max_n_masked(uint64_t lds_limit_bytes) {
+  if (lds_limit_bytes < kPptScratchBytes + 24) return 0;
+  return (lds_limit_bytes - kPptScratchBytes) / 24 * 64;
 }
 
 }  // namespace gs

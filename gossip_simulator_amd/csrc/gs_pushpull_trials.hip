@@ -7,8 +7,9 @@
 // global atomic and no launch per round: the words are loaded from the
 // context's recv bitset once, the rounds run between workgroup barriers, and
 // the words are stored back.  Draws, outcomes and counters are those of
-// k_pp_round (gs_pushpull.hip) with no failure mask, keyed by the trial's own
-// number: trial i of the batch is a one-trial context with params.trial + i.
+// k_pp_round (gs_pushpull.hip), keyed by the trial's own number: trial i of
+// the batch is a one-trial context with params.trial + i and, when the batch
+// has failure masks, trial i's mask (the kMasked instantiation below).
 //
 // Layout (the batched layout of gs_api.cpp): global node trial << tlog | v,
 // deg and rows at that index, the trial's informed words at word offset
@@ -45,12 +46,23 @@ __device__ __forceinline__ void wave_sums4(uint32_t* scratch, const uint32_t (&v
 // Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow) of every trial; row k of
 // a trial's tstat block gets round t0 + k's counters (TS_DEAD = kept pushes
 // that reached nobody: none without a failure mask).
+//
+// kMasked (per-trial failure masks, gs_set_failed on a batch): the trial's
+// failed set F is a third bitset in LDS (ppt_plan_masked), loaded once per
+// launch from the trial's words of s.crash and read-only.  k_pp_round's rules:
+// a failed v has degree 0 for the round (not fired, never calls); a kept push
+// to a failed u counts as sent and informs nobody (TS_DEAD); a pull needs no
+// check, an informed u being live.  The wave's own word of F is one
+// wave-uniform LDS read, a push target's failed bit one LDS gather.  The
+// unmasked instantiation has none of it.
+template <bool kMasked>
 __global__ __launch_bounds__(kPptMaxBlock) void k_ppt_rounds(const PptState s, uint32_t t0, uint32_t rounds) {
   extern __shared__ unsigned long long ppt_lds[];
   const uint32_t W = (s.n + 63) >> 6;
   unsigned long long* cur = ppt_lds;
   unsigned long long* next = ppt_lds + W;
-  uint32_t* scratch = (uint32_t*)(ppt_lds + 2 * (size_t)W);
+  unsigned long long* F = ppt_lds + 2 * (size_t)W;  // kMasked only; written by the load below alone
+  uint32_t* scratch = (uint32_t*)(ppt_lds + (kMasked ? 3 : 2) * (size_t)W);
   const uint32_t trial = blockIdx.x;
   const uint64_t base = (uint64_t)trial << s.tlog;
   unsigned long long* __restrict__ gw = s.recv + (base >> 6);
@@ -62,6 +74,10 @@ __global__ __launch_bounds__(kPptMaxBlock) void k_ppt_rounds(const PptState s, u
   uint32_t* __restrict__ rows = s.tstat + (size_t)trial * kMaxWindow * kTStatFields;
 
   for (uint32_t w = threadIdx.x; w < W; w += blockDim.x) cur[w] = gw[w];
+  if (kMasked) {
+    const unsigned long long* __restrict__ fw = s.crash + (base >> 6);
+    for (uint32_t w = threadIdx.x; w < W; w += blockDim.x) F[w] = fw[w];
+  }
   __syncthreads();
   for (uint32_t r = 0; r < rounds; ++r) {
     const uint32_t t = t0 + r;
@@ -71,7 +87,8 @@ __global__ __launch_bounds__(kPptMaxBlock) void k_ppt_rounds(const PptState s, u
     for (uint32_t w = wave; w < W; w += nwaves) {  // wave-uniform
       const uint32_t v = (w << 6) + lane;
       const unsigned long long Iw = cur[w];
-      const uint32_t d = v < s.n ? deg[v] : 0u;
+      uint32_t d = v < s.n ? deg[v] : 0u;
+      if (kMasked && ((F[w] >> lane) & 1)) d = 0;  // failed: never calls
       bool pulled = false;
       if (d > 0) {
         const u32x4 x = philox(v, t, 0, c3, s.key.k0, s.key.k1);
@@ -79,11 +96,13 @@ __global__ __launch_bounds__(kPptMaxBlock) void k_ppt_rounds(const PptState s, u
         const bool kept = (int32_t)uniform(x.y, 100u) >= s.kd;
         const unsigned long long ubit = 1ull << (u & 63);
         ++fired;
-        if ((Iw >> lane) & 1) {  // informed: push (no failure mask: every u is live)
+        if ((Iw >> lane) & 1) {  // informed: push (unmasked: every u is live)
           if (kept) {
             ++sent;
-            ++msgs;
-            if (u < s.n) atomicOr(&next[u >> 6], ubit);
+            if (!kMasked || u >= s.n || !(F[u >> 6] & ubit)) {  // u live: delivered
+              ++msgs;
+              if (u < s.n) atomicOr(&next[u >> 6], ubit);
+            }
           }
         } else if (kept && u < s.n && (cur[u >> 6] & ubit)) {  // pull from an informed u
           ++sent;
@@ -123,60 +142,85 @@ __global__ __launch_bounds__(kPptMaxBlock) void k_ppt_rounds(const PptState s, u
 
 // The sender of every trial is informed: `node` in each, or (~0u) the trial's
 // own keyed sender (simulator.go:240 per trial).  A thread per trial; trials
-// own disjoint words.
-__global__ void k_ppt_seed(const PptState s, uint32_t node) {
+// own disjoint words.  With a failure mask (s.crash) a trial whose sender is
+// failed stays empty, as k_pp_seed leaves a one-trial context; started[trial]
+// (when not null) = 1 if the trial's sender was informed.
+__global__ void k_ppt_seed(const PptState s, uint32_t node, uint32_t* __restrict__ started) {
   const uint32_t trial = blockIdx.x * blockDim.x + threadIdx.x;
   if (trial >= s.trials) return;
   uint32_t v = node;
   if (node == ~0u)
     v = uniform(philox(0, 0, 0, ctr3(K_SENDER, s.key.trial + trial), s.key.k0, s.key.k1).x, s.n);
   const uint64_t g = ((uint64_t)trial << s.tlog) + v;
-  s.recv[g >> 6] |= 1ull << (g & 63);
+  const unsigned long long bit = 1ull << (g & 63);
+  const bool ok = !s.crash || !(s.crash[g >> 6] & bit);
+  if (ok) s.recv[g >> 6] |= bit;
+  if (started) started[trial] = ok ? 1u : 0u;
 }
 
 // k_pp_live_edges restricted to one trial's rows and bits: live[trial] = 1 if
 // some informed node has an uninformed friend or some uninformed node an
 // informed one.  A workgroup per trial; only trials with need[trial] set are
 // scanned (those whose last poll informed nobody new).  live is zeroed by the
-// host; every writer stores the same 1.
+// host; every writer stores the same 1.  With a failure mask (s.crash) the
+// rule is k_pp_live_edges': a failed v makes no call, and an informed v's
+// failed friend cannot be informed (an informed friend is always live).
 __global__ __launch_bounds__(256) void k_ppt_stalled(const PptState s, const uint8_t* __restrict__ need,
                                                      uint32_t* __restrict__ live) {
   const uint32_t trial = blockIdx.x;
   if (!need[trial]) return;
   const uint64_t base = (uint64_t)trial << s.tlog;
   const unsigned long long* __restrict__ gw = s.recv + (base >> 6);
+  const unsigned long long* __restrict__ fw = s.crash ? s.crash + (base >> 6) : nullptr;
   const uint32_t tmask = (uint32_t)((1ull << s.tlog) - 1);
   bool any = false;
   for (uint32_t v = threadIdx.x; v < s.n && !any; v += blockDim.x) {
+    if (fw && ((fw[v >> 6] >> (v & 63)) & 1)) continue;
     const bool iv = (gw[v >> 6] >> (v & 63)) & 1;
     const uint32_t d = s.deg[base + v];
     for (uint32_t j = 0; j < d; ++j) {
       const uint32_t u = s.ids[(base + v) * s.stride + j] & tmask;
       if (u >= s.n) continue;
       const bool iu = (gw[u >> 6] >> (u & 63)) & 1;
-      if (iv != iu) { any = true; break; }
+      const bool fu = fw && ((fw[u >> 6] >> (u & 63)) & 1);
+      if (iv ? (!iu && !fu) : iu) { any = true; break; }
     }
   }
   if (any) live[trial] = 1u;
 }
 
-// What the device grants one workgroup of k_ppt_rounds: the reported
-// per-workgroup LDS, confirmed by asking the runtime whether a full block
-// with that much dynamic LDS can be resident; if it cannot, the 64 KiB every
-// HIP kernel may use without opting in.
-hipError_t ppt_lds_limit(int device, uint64_t* limit) {
+namespace {
+
+const void* rounds_kernel(bool masked) {
+  return masked ? (const void*)k_ppt_rounds<true> : (const void*)k_ppt_rounds<false>;
+}
+
+}  // namespace
+
+// What the device grants one workgroup of k_ppt_rounds (either
+// instantiation): the reported per-workgroup LDS, confirmed by asking the
+// runtime whether a full block with that much dynamic LDS can be resident; if
+// it cannot, the 64 KiB every HIP kernel may use without opting in.
+hipError_t ppt_lds_limit(int device, bool masked, uint64_t* limit, const char** where) {
   int dev0 = 0, v = 0;
+  const char* dummy;
+  if (!where) where = &dummy;
+  *where = "hipGetDevice";
   hipError_t e = hipGetDevice(&dev0);
   if (e != hipSuccess) return e;
+  *where = "hipSetDevice";
   if ((e = hipSetDevice(device)) != hipSuccess) return e;
+  *where = "hipDeviceGetAttribute(MaxSharedMemoryPerBlock)";
   e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
   if (e == hipSuccess) {
     uint64_t lim = v > 0 ? (uint64_t)v : 0;
     if (lim > 65536) {
       int nb = 0;
-      (void)hipFuncSetAttribute((const void*)k_ppt_rounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim);
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ppt_rounds, (int)kPptMaxBlock, (size_t)lim) != hipSuccess ||
-          nb < 1) {
+      (void)hipFuncSetAttribute(rounds_kernel(masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim);
+      const hipError_t oe =
+          masked ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ppt_rounds<true>, (int)kPptMaxBlock, (size_t)lim)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ppt_rounds<false>, (int)kPptMaxBlock, (size_t)lim);
+      if (oe != hipSuccess || nb < 1) {
         (void)hipGetLastError();
         lim = 65536;
       }
@@ -187,27 +231,34 @@ hipError_t ppt_lds_limit(int device, uint64_t* limit) {
   return e;
 }
 
-// Past the default 64 KiB of dynamic LDS a kernel opts in, per device: once
-// per context, at create (raising the limit again is idempotent).
-hipError_t ppt_prepare(int device, uint32_t lds_bytes) {
+// Past the default 64 KiB of dynamic LDS a kernel opts in, per device and per
+// instantiation: the unmasked one once per context, at create; the masked one
+// when the context gets its mask (raising the limit again is idempotent).
+hipError_t ppt_prepare(int device, bool masked, uint32_t lds_bytes) {
   int dev0 = 0;
   hipError_t e = hipGetDevice(&dev0);
   if (e != hipSuccess) return e;
   if ((e = hipSetDevice(device)) != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)k_ppt_rounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  e = hipFuncSetAttribute(rounds_kernel(masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   (void)hipSetDevice(dev0);
   return e;
 }
 
+// s.crash set: the masked instantiation with the masked plan's LDS.
 hipError_t ppt_rounds(const PptState& s, uint32_t t0, uint32_t rounds, hipStream_t st) {
   if (rounds == 0) return hipSuccess;
   if (rounds > kMaxWindow) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_ppt_rounds, dim3(s.trials), dim3(s.block), s.lds_bytes, st, s, t0, rounds);
+  if (s.crash) {
+    if (s.lds_masked == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ppt_rounds<true>, dim3(s.trials), dim3(s.block), s.lds_masked, st, s, t0, rounds);
+  } else {
+    hipLaunchKernelGGL(k_ppt_rounds<false>, dim3(s.trials), dim3(s.block), s.lds_bytes, st, s, t0, rounds);
+  }
   return hipGetLastError();
 }
 
-hipError_t ppt_seed(const PptState& s, uint32_t node, hipStream_t st) {
-  hipLaunchKernelGGL(k_ppt_seed, dim3((s.trials + 255) / 256), dim3(256), 0, st, s, node);
+hipError_t ppt_seed(const PptState& s, uint32_t node, uint32_t* started, hipStream_t st) {
+  hipLaunchKernelGGL(k_ppt_seed, dim3((s.trials + 255) / 256), dim3(256), 0, st, s, node, started);
   return hipGetLastError();
 }
 

@@ -1946,7 +1946,11 @@ __device__ __forceinline__ void resolve_small_bucket(const WinState& w, uint32_t
   }
 }
 
-__global__ void k_schedule_win(const WinState w, uint32_t node, uint32_t t, uint32_t trials, uint32_t n) {
+// started (batched trials with per-trial failure masks, else null): a failed
+// sender never broadcasts, so its trial schedules nothing; started[i] = 1 for
+// the trials that did.
+__global__ void k_schedule_win(const WinState w, uint32_t node, uint32_t t, uint32_t trials, uint32_t n,
+                               uint32_t* __restrict__ started) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= trials) return;
   uint32_t local = node;
@@ -1954,6 +1958,11 @@ __global__ void k_schedule_win(const WinState w, uint32_t node, uint32_t t, uint
     uint32_t v = node;
     if (node == ~0u) v = uniform(philox(0, 0, 0, ctr3(K_SENDER, w.key.trial + i), w.key.k0, w.key.k1).x, n);
     local = (i << w.tlog) | v;  // batched contexts have base 0
+  }
+  if (started) {
+    const bool dead = (w.crash[local >> 6] >> (local & 63)) & 1;
+    started[i] = dead ? 0u : 1u;
+    if (dead) return;
   }
   uint32_t kn, c3;
   node_key(w.tlog, w.tmask, w.key, (uint64_t)w.base + local, K_DELAY, kn, c3);
@@ -2604,8 +2613,8 @@ hipError_t win_stats_reduce(const WinState& w, uint32_t t0, uint32_t L, hipStrea
 }
 
 hipError_t win_schedule(const WinState& w, uint32_t node, uint32_t tick, uint32_t trials, uint32_t n,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(k_schedule_win, dim3((trials + 255) / 256), dim3(256), 0, s, w, node, tick, trials, n);
+                        hipStream_t s, uint32_t* started) {
+  hipLaunchKernelGGL(k_schedule_win, dim3((trials + 255) / 256), dim3(256), 0, s, w, node, tick, trials, n, started);
   return hipGetLastError();
 }
 

@@ -240,7 +240,13 @@ class Simulator:
         return deg, ids
 
     def set_failed(self, words: np.ndarray):
+        """Pre-failed nodes (gs_set_failed), before broadcast_begin: ceil(n/64)
+        words.  Batched trials: one mask per trial, [trials, ceil(n/64)] or the
+        same flat, trial-major; a Simulator.rank context takes the masks of its
+        own trials only ([self.trials, ceil(n/64)])."""
         words = np.ascontiguousarray(words, dtype=np.uint64)
+        if words.ndim == 2 and words.shape != (self.trials, self.words):
+            raise ValueError(f"masks must be [{self.trials}, {self.words}] (or flat), not {list(words.shape)}")
         self._check(self.L.gs_set_failed(self.h, words.ctypes.data, words.size), "gs_set_failed")
 
     # -- broadcast (simulator.go:107-123, 140-149, 237-253) ----------------
@@ -352,7 +358,21 @@ def pp_trials_max_n(device: int = 0) -> int:
     out = C.c_uint64(0)
     rc = L.gs_pp_trials_max_n(int(device), C.byref(out))
     if rc != 0:
-        raise GossipError(rc, "gs_pp_trials_max_n failed")
+        why = L.gs_last_error(None).decode(errors="replace")
+        raise GossipError(rc, "gs_pp_trials_max_n failed" + (f" ({why})" if why and why != "NULL context" else ""))
+    return int(out.value)
+
+
+def pp_trials_max_n_masked(device: int = 0) -> int:
+    """Largest n a batched push-pull context may have on `device` when it is
+    given failure masks (gs_pp_trials_max_n_masked): the trial's failed set is
+    a third bitset in the workgroup's LDS."""
+    L = _lib.load()
+    out = C.c_uint64(0)
+    rc = L.gs_pp_trials_max_n_masked(int(device), C.byref(out))
+    if rc != 0:
+        why = L.gs_last_error(None).decode(errors="replace")
+        raise GossipError(rc, "gs_pp_trials_max_n_masked failed" + (f" ({why})" if why and why != "NULL context" else ""))
     return int(out.value)
 
 

@@ -66,7 +66,9 @@ enum {
                               * (oracle/gsoracle.h).  With trials > 1:
                               * one workgroup per trial, the trial's informed set in LDS, so
                               * n <= gs_pp_trials_max_n(); the GS_FLAG_PP_* round modes are
-                              * accepted and ignored (there is one round kind) */
+                              * accepted and ignored (there is one round kind); gs_set_failed
+                              * takes one mask per trial (a third bitset in LDS, so then
+                              * n <= gs_pp_trials_max_n_masked()) */
 
 /* simulator.go:11-20 (Parameters) + the additive -seed/-trial knobs. */
 typedef struct gs_params {
@@ -238,6 +240,11 @@ const char* gs_last_error(const gs_ctx* ctx);
  * trials > 1 with GS_MODEL_PUSHPULL, as it did before the combination
  * existed; every other create, and this query, then fail with GS_EDEVICE.) */
 int gs_pp_trials_max_n(int device, uint64_t* n_max);
+/* The same for a batched push-pull context that is given failure masks
+ * (gs_set_failed): the trial's failed set is a third bitset in LDS, so this
+ * limit is about two thirds of gs_pp_trials_max_n's.  A context past it runs
+ * unmasked; gs_set_failed refuses it with GS_EINVAL. */
+int gs_pp_trials_max_n_masked(int device, uint64_t* n_max);
 
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
@@ -259,7 +266,18 @@ int gs_build_overlay(gs_ctx* ctx, uint64_t max_ticks, gs_window* win, size_t cap
 
 /* Pre-failed node mask (extension, config C5): words[ceil(n/64)], set bits
  * are crash-stopped before the broadcast: they never count nor forward, and
- * a failed sender does not broadcast (both models).  Not for batched trials. */
+ * a failed sender does not broadcast (both models).  Set before
+ * gs_broadcast_begin; kept by gs_reset and gs_set_trial.
+ * Batched trials (both models): one mask per trial, trials x ceil(n/64)
+ * words, trial-major (the layout of gs_read_received / gs_read_crashed; fewer
+ * words: GS_EINVAL); bits at or past n in a trial's last word are ignored.
+ * Trial i with its mask behaves exactly like a one-trial context of trial
+ * params.trial + i given that mask; a trial whose sender is failed never
+ * starts and stops at its first poll while the others run on.  A context
+ * made by gs_create_multi hands each member its trials' slice; one made by
+ * gs_create_rank takes the masks of that rank's trials only.  A push-pull
+ * batch needs n <= gs_pp_trials_max_n_masked() (else GS_EINVAL, and the
+ * context stays usable without a mask). */
 int gs_set_failed(gs_ctx* ctx, const uint64_t* words, size_t nwords);
 
 /* Replaces simulator.go:239-241.  sender < 0 draws it from the keyed stream
