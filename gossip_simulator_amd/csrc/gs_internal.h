@@ -273,7 +273,7 @@ hipError_t win_stats_reduce(const WinState& w, uint32_t t0, uint32_t L, hipStrea
 // node-range shards
 hipError_t win_consume_sh(const WinState& w, uint32_t t0, uint32_t L, hipStream_t s);
 // device-driven shard windows (w.dd): the receive layout of shard w.rank from
-// the gathered fills (rtab as gs_api.cpp's shard_exchange lays it out;
+// the gathered fills (rtab as gs_shards.cpp's shard_exchange lays it out;
 // ccaps[s] = sender s's region starts, in place unless `travels`; src[] the
 // layout's source buffers); the exact fine re-partition guarded by kErrFine;
 // the window's counters into w.wstat; the close over the G shards' wstat

@@ -11,7 +11,7 @@
 // the batch is a one-trial context with params.trial + i and, when the batch
 // has failure masks, trial i's mask (the kMasked instantiation below).
 //
-// Layout (the batched layout of gs_api.cpp): global node trial << tlog | v,
+// Layout (the batched layout of gs_ctx.cpp): global node trial << tlog | v,
 // deg and rows at that index, the trial's informed words at word offset
 // (trial << tlog) / 64 of recv (tlog >= 14: whole words, disjoint per trial).
 // Padding nodes v >= n of a trial's slot never call and are never counted.

@@ -273,7 +273,7 @@ __device__ __forceinline__ void cut_body(const WinState& w, unsigned long long b
       s_L = L;
       c->tnext = t + L;
       c->Tn = Tn;
-      // owner expand (shards): the plan of gs_api.cpp's plan_coarse_owner over
+      // owner expand (shards): the plan of gs_shards.cpp's plan_coarse_owner over
       // the longest row; unsharded: over the stride
       c->T = Tn * (w.owner ? w.slots : w.stride);
       s_T = c->T;
@@ -2038,7 +2038,7 @@ __device__ __forceinline__ unsigned long long block_exscan_u64(unsigned long lon
 }
 
 // ---- device-driven shard windows ------------------
-// The host-driven shard window (gs_api.cpp shard_windows) reads every shard's
+// The host-driven shard window (gs_shards.cpp shard_windows) reads every shard's
 // fire counts and region fills on the host to cut the window and lay out the
 // receive side.  Here the counts and fills are gathered into device buffers
 // (RCCL all-gathers between ranks; the shards of one device share them), every
@@ -2430,7 +2430,7 @@ hipError_t win_groupmap(const WinState& w, uint32_t L, hipStream_t s) {
 // mode 0: count coarse buckets only; 1: write + per-tick stats; 2: write only
 // k_expand's launch geometry for a window of Tn firing nodes: firing nodes per
 // round, workgroup size, grid.  One source for win_expand and for the host's
-// per-XCD region plan of batched trials (plan_coarse_trials, gs_api.cpp),
+// per-XCD region plan of batched trials (plan_coarse_trials, gs_windows.cpp),
 // which must know which sub-region each round writes (xcd_rounds).
 uint32_t win_expand_geometry(const WinState& w, uint64_t Tn, uint32_t* per_round_out, uint32_t* bsz_out,
                              uint32_t* npt_out) {

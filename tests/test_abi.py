@@ -103,7 +103,7 @@ def test_product_philox_matches_kat(L):
 
 
 def test_stride_magic_division_exact():
-    # gs_api.cpp: q / S == umulhi(q, floor(2^32/S) + 1) for q < 1024*255, S in [2, 255]
+    # gs_peers.cpp (set_stride): q / S == umulhi(q, floor(2^32/S) + 1) for q < 1024*255, S in [2, 255]
     import numpy as np
     q = np.arange(0, 1024 * 255 + 1, dtype=np.uint64)
     for S in range(2, 256):

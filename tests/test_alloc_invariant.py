@@ -61,7 +61,8 @@ def test_product_never_uses_the_stream_ordered_pool():
 
 def test_the_scan_sees_every_product_source():
     names = {os.path.basename(p) for p in _sources()}
-    for must in ("gs_overlay.hip", "gs_window.hip", "gs_pushpull.hip", "gs_api.cpp", "gossip.h"):
+    for must in ("gs_overlay.hip", "gs_window.hip", "gs_pushpull.hip", "gs_api.cpp", "gossip.h", "gs_ctx.h",
+                 "gs_ctx.cpp", "gs_peers.cpp", "gs_windows.cpp", "gs_shards.cpp", "gs_pushpull_host.cpp"):
         assert must in names
 
 

@@ -3,7 +3,7 @@
 * Trial sharding: dist.run_trials (the product's host code) over gloo, with the
   oracle behind the batch interface the HIP engine exposes -- must reproduce
   the serial trials.
-* Node-range sharding: the library's window protocol (gs_api.cpp
+* Node-range sharding: the library's window protocol (gs_shards.cpp
   shard_windows: the same window cut on every shard from the gathered fire
   counts, every message of the window delivered to the shard that owns its
   target, per-poll sum of the counters) restated over oracle shards and gloo
@@ -14,7 +14,7 @@
   on the GPU (tests/test_gpu_multi.py, and with two processes exchanging
   through gloo in tests/test_rank_exchange.py).
 * Push-pull node-range sharding (config C5): the sharded rounds of
-  gs_api.cpp pp_shard_step -- bottom-up on the shard's own nodes against the
+  gs_pushpull_host.cpp pp_shard_step -- bottom-up on the shard's own nodes against the
   replicated informed set, then an all-gather of the owned words; and
   pull-answer, the shard's informed nodes informing nodes anywhere, whose
   bits go to their owners -- restated in numpy over gloo; each must equal the
@@ -76,7 +76,7 @@ class OracleBatch:
 
 
 def run_sharded_model(O, p, deg, ids, rank, world, poll=10):
-    """The window protocol of the sharded engine (gs_api.cpp shard_windows),
+    """The window protocol of the sharded engine (gs_shards.cpp shard_windows),
     restated over oracle shards: a window of L = min(max(delaylow,1), 10)
     ticks (never crossing a poll) starts by all-gathering every shard's firing
     sets of its L ticks -- all already scheduled, since a Broadcast fires at
@@ -359,7 +359,7 @@ def test_pushpull_node_range_sharding_world2_bit_identical(oracle, tmp_path):
 
 
 def test_pushpull_pull_answer_sharding_world2_bit_identical(oracle, tmp_path):
-    """The sharded pull-answer round (gs_api.cpp pp_shard_step, k_ppa_round on
+    """The sharded pull-answer round (gs_pushpull_host.cpp pp_shard_step, k_ppa_round on
     each shard's informed nodes, their bits in other ranges sent to the owners)
     restated over gloo, every round pull-answer: equal to the oracle's
     unsharded pushpull_step per round, 2 % failed."""
