@@ -7,6 +7,7 @@ Layers:
   csrc/gs_window.hip        window engine: expand, partition, resolve (default)
   csrc/gs_pushpull.hip      push-pull rounds (extension, config C5)
   csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
+  csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI entry points: argument checks, dispatch by context kind
   csrc/gs_ctx.h, gs_ctx.cpp the context behind the ABI: set-up and release of every kind
@@ -14,6 +15,7 @@ Layers:
   csrc/gs_windows.cpp       host side of the unsharded flood: host- and device-driven windows
   csrc/gs_shards.cpp        host side of flood node-range shards and their exchanges
   csrc/gs_pushpull_host.cpp host side of push-pull: sparse rounds, shards, batched trials
+  csrc/gs_rumor_host.cpp    host side of rumor mongering: buffers, round loop, stop rule
   csrc/gs_devmem.cpp        process-wide cache of large device blocks (gs_trim)
   csrc/gossip_sim.cpp       CLI with the reference's flags and stdout
   engine.py                 Python host API (ctypes)

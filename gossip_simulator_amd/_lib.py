@@ -23,7 +23,7 @@ GS_FLAG_PP_EARLY = 16
 GS_FLAG_PP_TOPDOWN = 32
 GS_FLAG_PP_BOTTOM = 64
 GS_FLAG_PP_ANSWER = 128
-GS_MODEL_FLOOD, GS_MODEL_PUSHPULL = 0, 1
+GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR = 0, 1, 2
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
 GS_COMM_ID_BYTES = 128
 
@@ -37,7 +37,7 @@ EXPORTS = (
     "gs_set_flags", "gs_reset", "gs_set_stream", "gs_create_multi", "gs_comm_unique_id",
     "gs_create_rank", "gs_shard_info", "gs_trial_results", "gs_set_trial",
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
-    "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked",
+    "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
 )
 
 
@@ -60,9 +60,9 @@ class Params(C.Structure):
         ("trial", C.c_uint32),
         ("device", C.c_int32),
         ("flags", C.c_uint32),
-        ("model", C.c_uint32),  # GS_MODEL_FLOOD = 0 (reference), GS_MODEL_PUSHPULL = 1
+        ("model", C.c_uint32),  # GS_MODEL_FLOOD = 0 (reference), GS_MODEL_PUSHPULL = 1, GS_MODEL_RUMOR = 2
         ("trials", C.c_uint32),  # batched independent trials (config C3); 0/1 = one
-        ("reserved0_", C.c_uint32),
+        ("rumor_k", C.c_uint32),  # GS_MODEL_RUMOR: misses after which a node stops calling (1..255)
         ("reserved_", C.c_uint64 * 5),
     ]
 
@@ -140,6 +140,7 @@ def load():
         "gs_totals": ([ctx, P(TickStats)], C.c_int),
         "gs_read_received": ([ctx, vp, sz], C.c_int),
         "gs_read_crashed": ([ctx, vp, sz], C.c_int),
+        "gs_read_removed": ([ctx, vp, sz], C.c_int),
         "gs_timing_get": ([ctx, P(Timing)], C.c_int),
         "gs_shard_timing": ([ctx, C.c_uint32, P(Timing)], C.c_int),
         "gs_format_float32": ([C.c_float, C.c_char_p, sz], sz),

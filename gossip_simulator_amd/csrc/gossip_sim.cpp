@@ -4,8 +4,9 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -trials -device -peers -maxticks) are not echoed in the
-// parameter block, so stdout keeps the reference's shape.  -trials T > 1 runs
+// (-seed -trial -trials -device -peers -maxticks -model -k) are not echoed in
+// the parameter block, so stdout keeps the reference's shape.  -model rumor
+// runs to its own end and adds the residue and the messages per node.  -trials T > 1 runs
 // T independent trials in one batched context and prints one line per trial.
 #include <chrono>
 #include <cinttypes>
@@ -193,12 +194,26 @@ int main(int argc, char** argv) {
       {"gpus", "int", "node-range shards over devices device .. device+gpus-1 (one process)", "1", false,
        "1"},
       {"peers", "string", "injected peer-table file (skips overlay construction)", "", false, ""},
-      {"model", "string", "dissemination model: flood (the reference) or pushpull (extension)",
+      {"model", "string", "dissemination model: flood (the reference), pushpull or rumor (extensions)",
        "flood", false, "flood"},
+      {"k", "int", "rumor model: a node stops calling after this many calls that reached an informed peer",
+       "2", false, "2"},
       {"maxticks", "int", "give up after this many simulated ms per phase", "10000000", false,
        "10000000"},
   };
   parse(argc, argv);
+  // every flag is checked before the parameter echo and before any device call
+  const std::string model = find("model")->val;
+  if (model != "flood" && model != "pushpull" && model != "rumor") {
+    fprintf(stderr, "invalid value \"%s\" for flag -model: want flood, pushpull or rumor\n", model.c_str());
+    return 2;
+  }
+  const long long rumor_k = ival("k");
+  if (model == "rumor" && (rumor_k < 1 || rumor_k > 255)) {
+    fprintf(stderr, "invalid value \"%s\" for flag -k: want 1..255\n", find("k")->val.c_str());
+    usage();
+    return 2;
+  }
 
   printf("=== Parameters ===\n");                              // :197-204
   {
@@ -223,12 +238,8 @@ int main(int argc, char** argv) {
   p.seed = strtoull(find("seed")->val.c_str(), nullptr, 10);
   p.trial = (uint32_t)strtoull(find("trial")->val.c_str(), nullptr, 10);
   p.device = (int32_t)ival("device");
-  const std::string model = find("model")->val;
-  if (model != "flood" && model != "pushpull") {
-    fprintf(stderr, "invalid value \"%s\" for flag -model: want flood or pushpull\n", model.c_str());
-    return 2;
-  }
-  p.model = model == "pushpull" ? GS_MODEL_PUSHPULL : GS_MODEL_FLOOD;
+  p.model = model == "pushpull" ? GS_MODEL_PUSHPULL : model == "rumor" ? GS_MODEL_RUMOR : GS_MODEL_FLOOD;
+  if (p.model == GS_MODEL_RUMOR) p.rumor_k = (uint32_t)rumor_k;
   const uint64_t max_ticks = (uint64_t)ival("maxticks");
   const long long ntrials = ival("trials");
   if (ntrials < 1 || ntrials > 0x7FFFFFFFll) {
@@ -324,6 +335,19 @@ int main(int argc, char** argv) {
   gs_tick_stats tot{};
   gs_totals(c, &tot);
   const double bc_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
+  if (p.model == GS_MODEL_RUMOR) {  // the model's own outputs, at quiescence
+    char rb[64], mb[64];
+    gs_format_float32(1.0f - (float)tot.received / (float)p.n, rb, sizeof(rb));
+    gs_format_float32((float)tot.messages / (float)p.n, mb, sizeof(mb));
+    printf("--- Residue %s, %s messages per node after %s ---\n", rb, mb, dur_ms(tot.tick).c_str());
+    if (status == GS_RUN_QUIESCENT) {  // the model's normal end: it fell quiet below 99 %
+      printf("\nTotal message %" PRIu64 " Total Crashed %" PRIu64 "\n", tot.messages, tot.crashed);
+      fflush(stdout);
+      fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, broadcast %.3f s\n", ov_wall, bc_wall);
+      gs_destroy(c);
+      return 0;
+    }
+  }
   if (status != GS_RUN_COVERED) {
     fflush(stdout);
     fprintf(stderr, "%s: %s before 99%% coverage (the reference would poll forever)\n", g_prog,
@@ -331,7 +355,13 @@ int main(int argc, char** argv) {
     gs_destroy(c);
     return 3;
   }
-  printf("--- Took %s to get 99%% ---\n\n", dur_ms(tot.tick).c_str());  // :252
+  uint64_t t99 = tot.tick;
+  if (p.model == GS_MODEL_RUMOR) {  // the run went on to quiescence: the first covered poll
+    gs_trial_stats tr{};
+    size_t ntr = 0;
+    if (gs_trial_results(c, &tr, 1, &ntr) == GS_OK && ntr == 1 && tr.tick_99) t99 = tr.tick_99;
+  }
+  printf("--- Took %s to get 99%% ---\n\n", dur_ms(t99).c_str());  // :252
   printf("Total message %" PRIu64 " Total Crashed %" PRIu64 "\n", tot.messages, tot.crashed); // :253
   fflush(stdout);
   fprintf(stderr,

@@ -28,7 +28,18 @@ int check_params(const gs_params* p, std::string& why) {
     return GS_EINVAL;
   }
   if (ring_slots(*p) > 4096) { why = "delayhigh must be <= 4096"; return GS_EINVAL; }
-  if (p->model > GS_MODEL_PUSHPULL) { why = "model must be GS_MODEL_FLOOD or GS_MODEL_PUSHPULL"; return GS_EINVAL; }
+  if (p->model > GS_MODEL_RUMOR) {
+    why = "model must be GS_MODEL_FLOOD, GS_MODEL_PUSHPULL or GS_MODEL_RUMOR";
+    return GS_EINVAL;
+  }
+  if (p->model == GS_MODEL_RUMOR && (p->rumor_k < 1 || p->rumor_k > 255)) {
+    why = "GS_MODEL_RUMOR needs 1 <= rumor_k <= 255, not " + std::to_string(p->rumor_k);
+    return GS_EINVAL;
+  }
+  if (p->model == GS_MODEL_RUMOR && p->trials > 1) {
+    why = "GS_MODEL_RUMOR with trials > 1: the rumor model runs one trial per context (batched trials are not built)";
+    return GS_EINVAL;
+  }
   // batched trials (either model) live at trial << tlog | node in one 31-bit id space
   if (p->trials > 1 && ((uint64_t)p->trials << std::max<uint32_t>(kFineLog, ceil_log2(p->n))) > 0x7FFFFFFFull) {
     why = "trials x 2^ceil(log2 n) must be < 2^31 (batch fewer trials per context)";
@@ -184,6 +195,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   DevState& s = c->st;
   const uint32_t stride0 = (uint32_t)std::max(c->p.fanout, c->p.fanin);
   c->pp = c->p.model == GS_MODEL_PUSHPULL;
+  c->rumor = c->p.model == GS_MODEL_RUMOR;
   c->pp_l2_only = (c->p.flags & GS_FLAG_PP_L2_ONLY) != 0;
   c->trials = std::max<uint32_t>(1, c->p.trials);
   c->ntot = c->p.n;
@@ -194,6 +206,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   c->shard = shard;
   c->G = G;
   c->rank = rank;
+  if (shard && c->rumor) {
+    why = "GS_MODEL_RUMOR runs on one device: no node-range shards";
+    return GS_EINVAL;
+  }
   if (shard) {
     if (c->pp && !pp_rslot_packed(stride0)) {
       why = "push-pull node-range shards need rows of at most 16 slots (bottom-up rounds)";
@@ -229,7 +245,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // Engine: the window engine unless the ring is too long for LDS, rows are
   // wider than 32 or the tick engine is forced; push-pull has its own kernels.
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
-  c->win = !c->pp && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
+  c->win = !c->pp && !c->rumor && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
   if (((c->trials > 1 && !c->ppt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
@@ -248,9 +264,11 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // One state allocation, 256-B aligned sub-buffers; everything before
   // `stats` is per-broadcast state that gs_reset clears.
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const bool tick = !c->win && !c->pp;
-  // (batched push-pull trials build `next` in LDS: no second bitset, no summaries)
-  const size_t b_next = c->pp && !c->ppt ? al(s.W * 8) + al(pp_summary_total_words(s.W) * 8) : 0;
+  const bool tick = !c->win && !c->pp && !c->rumor;
+  // (batched push-pull trials build `next` in LDS: no second bitset, no summaries;
+  // the rumor model has the second bitset and no summaries)
+  const size_t b_sum = c->pp && !c->ppt ? al(pp_summary_total_words(s.W) * 8) : 0;
+  const size_t b_next = (c->pp && !c->ppt) || c->rumor ? al(s.W * 8) + b_sum : 0;
   const size_t b_bits = al(s.W * 8), b_ring = tick ? al((size_t)s.R * s.W * 8) : 0,
                b_cflag = tick ? al((size_t)s.R * s.C * 4) : 0,
                b_clist = tick ? al((size_t)s.R * kShards * s.CS * 4) : 0,
@@ -268,7 +286,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   s.crash = (unsigned long long*)q; q += b_bits;
   s.rollw = b_roll ? (uint32_t*)q : nullptr; q += b_roll;
   c->d_next = b_next ? (unsigned long long*)q : nullptr;
-  c->d_ppsum = b_next ? (unsigned long long*)(q + al(s.W * 8)) : nullptr;
+  c->d_ppsum = b_sum ? (unsigned long long*)(q + al(s.W * 8)) : nullptr;
   q += b_next;
   s.ring = (unsigned long long*)q; q += b_ring;
   s.cflag = (uint32_t*)q; q += b_cflag;
@@ -288,6 +306,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   s.cnt = c->d_cnt;
   if (c->win) {
     int rc = alloc_window(c);
+    if (rc) { why = c->err; return rc; }
+  }
+  if (c->rumor) {
+    int rc = rumor_alloc(c);
     if (rc) { why = c->err; return rc; }
   }
   if (c->ppt) {  // per-trial counter rows and the stall check's buffers
@@ -495,6 +517,7 @@ int finish_rank(gs_ctx* c, gs_ctx** out) {
 // The body of gs_create_multi: shards of one broadcast, or trial batches,
 // over `devices`.
 int create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out) {
+  RC(rumor_refuse(params, "gs_create_multi"));
   gs_ctx* g = new gs_ctx();
   g->group = true;
   g->p = *params;
@@ -715,6 +738,7 @@ void destroy_one(gs_ctx* c) {
   release_window(c);
   release_trials(c);
   release_sparse(c);
+  release_rumor(c);
   release_async(c);
   release_dd(c);
   if (c->own) (void)hipStreamDestroy(c->own);

@@ -1,7 +1,8 @@
 // gs_ctx.h -- the context behind the C ABI, private to csrc/: struct gs_ctx,
 // the error macros and the few host functions that cross the engine files
 // (gs_ctx.cpp lifetime, gs_peers.cpp tables, gs_windows.cpp / gs_shards.cpp
-// the flood engines, gs_pushpull_host.cpp push-pull, gs_api.cpp the entry points).
+// the flood engines, gs_pushpull_host.cpp push-pull, gs_rumor_host.cpp rumor
+// mongering, gs_api.cpp the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,6 +94,16 @@ struct PpSparseBufs {
   // push-pull: live callers and live empty rows of (cl_tver, cl_fver) (pp_seed_ctx)
   uint64_t cl_tver = ~0ull, cl_fver = ~0ull;
   unsigned long long cl_counts[2] = {0, 0};
+};
+
+// rumor mongering (gs_rumor.hip): the two hot lists [n] u32, the miss counts
+// [n] u8, round control (RumorCtl) and, once gs_read_removed asks, the removed
+// bitset [W]: rumor_alloc / release_rumor
+struct RumorBufs {
+  Buf list[2], miss, ctlb, removed;
+  uint32_t cur = 0;   // list[cur] is the next round's read list
+  uint32_t grid = 0;  // the round kernel's persistent grid (rumor_begin)
+  RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
 };
 
 // batched trials' per-trial counter rows (both models) and the push-pull
@@ -191,6 +202,9 @@ struct gs_ctx {
   uint64_t table_ver = 0, fail_ver = 0;
   gs::PPSparse sp{};
   gs::PpSparseBufs sr;
+  // rumor mongering (gs_rumor.hip; d_next is its informed set being built)
+  bool rumor = false;
+  gs::RumorBufs rm;
   // window engine (gs_window.hip)
   bool win = false;
   gs::WinState ws{};
@@ -371,5 +385,15 @@ int ppt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out);
 int ppt_poll_stops(gs_ctx* c, const std::vector<uint64_t>& r0, uint64_t max_ticks, uint32_t* running);
 void snap_trial(gs_ctx* c, uint32_t tr, int32_t status);
 bool trials_stopped(const gs_ctx* c, uint32_t running, int32_t* st);
+
+// gs_rumor_host.cpp
+int rumor_refuse(const gs_params* params, const char* what);
+int rumor_alloc(gs_ctx* c);
+void release_rumor(gs_ctx* c);
+int rumor_begin(gs_ctx* c, uint64_t sender);
+int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls);
+int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+              int32_t* status);
+int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
 
 }  // namespace gs

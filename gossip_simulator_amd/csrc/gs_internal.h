@@ -502,6 +502,50 @@ hipError_t ppt_rounds(const PptState& s, uint32_t t0, uint32_t rounds, hipStream
 // live[trial] = 1 where need[trial] and a call could still inform someone (live zeroed by the caller).
 hipError_t ppt_stalled(const PptState& s, const uint8_t* need, uint32_t* live, hipStream_t st);
 
+// Rumor mongering (gs_rumor.hip): a list engine.  The
+// hot set (informed, live, a friend to call, fewer than k misses) is a u32
+// list; each round walks the read list a lane per entry and builds the write
+// list, and the two swap.  `next` is the informed set being built (equal to
+// recv at the start of every round), miss the per-node miss counts.
+// Round control.  The words many workgroups add to -- the write list's append
+// cursor and the round's counters -- each sit on a 256-byte block of their own
+// (counter layout); the rest is written by one lane per
+// round (k_rumor_publish) and read by the next round's kernels.
+enum RumorAcc : uint32_t { RA_FIRED = 0, RA_SENT = 1, RA_MSGS = 2, RA_NEW = 3 };
+constexpr uint32_t kRumorCovered = 1, kRumorQuiescent = 2;  // RumorCtl::stop: 1 + GS_RUN_*
+struct RumorCtl {
+  unsigned long long wlen;      // entries appended to the write list this round
+  unsigned long long pad0_[31];
+  unsigned long long acc[4];    // the round's fired / sent / messages / newly informed (RumorAcc)
+  unsigned long long pad1_[28];
+  unsigned long long rlen;      // entries of the read list: the hot nodes
+  unsigned long long received;  // |I|
+  unsigned long long cover;     // smallest |I| the float32 coverage rule accepts
+  unsigned long long peak;      // largest hot set since the broadcast began
+  uint32_t stop, pad2_;         // 0 while a node is hot; else kRumorCovered / kRumorQuiescent
+  unsigned long long pad3_[27];
+};
+static_assert(sizeof(RumorCtl) == 3 * 256, "RumorCtl: three 256-byte blocks");
+struct RumorState {
+  RumorCtl* ctl;
+  unsigned long long* next;     // [W] informed set being built
+  uint8_t* miss;                // [n] kept calls that reached an informed peer; written by v's own lane only
+  uint32_t k;                   // misses after which a node is removed (gs_params.rumor_k)
+};
+// The persistent round grid for n nodes: `want` blocks (0: 256 CUs x 8), at most one lane per node.
+uint32_t rumor_grid(uint64_t n, uint32_t want);
+// ctl zeroed by the caller; the sender is informed unless failed, and listed in list0 if it has a friend.
+hipError_t rumor_seed(const DevState& s, const RumorState& r, uint32_t* list0, uint32_t node, unsigned long long cover,
+                      hipStream_t st);
+// Round t: rlist (ctl->rlen entries) -> wlist; a no-op on an empty list.
+hipError_t rumor_round(const DevState& s, const RumorState& r, const uint32_t* rlist, uint32_t* wlist, uint32_t t,
+                       uint32_t grid, hipStream_t st);
+// recv = next, then round t's stats row (ST_SCHED = the hot nodes after the round), list length and stop word.
+hipError_t rumor_commit(const DevState& s, const RumorState& r, uint32_t t, hipStream_t st);
+// out (holding a copy of recv) &= ~(the nodes of rlist): the removed set.
+hipError_t rumor_removed(const RumorState& r, const uint32_t* rlist, unsigned long long* out, uint32_t grid,
+                         hipStream_t st);
+
 // Launchers (gs_broadcast.hip).
 hipError_t launch_tick(const DevState& st, uint32_t tick, int mode, hipStream_t s);
 hipError_t launch_slot_reset(const DevState& st, uint32_t slot, hipStream_t s);

@@ -15,6 +15,7 @@
 //   kind PUSHPULL (extension)        ctr {v, t, 0, .}            out[0] -> U_deg, out[1] -> U_100
 //   kind ORDER   simulator.go:107-115 ctr {u, t, (g-1)/4, .}    out[(g-1)%4] -> U_(k-g+1): receipt
 //                                   order, first_crash() below
+//   kind RUMOR (extension)           ctr {v, t, 0, .}            out[0] -> U_deg, out[1] -> U_100
 // with counter word 3 = kind << 24 | trial.  U_m(r) = floor(r*m / 2^32).
 #pragma once
 #include <stdint.h>
@@ -26,7 +27,8 @@ enum Kind : uint32_t {
   K_SENDER = 1, K_DELAY = 2, K_DROP = 3, K_CRASH = 4,  // K_CRASH: reserved (round 2's crash-roll stream)
   K_PICK = 5, K_OVDELAY = 6, K_VICTIM = 7, K_REPLACE = 8,
   K_PUSHPULL = 9,  // push-pull extension: peer pick + loss per (node, round)
-  K_ORDER = 10     // receipt order of a (node, tick): first-crash position
+  K_ORDER = 10,    // receipt order of a (node, tick): first-crash position
+  K_RUMOR = 11     // rumor mongering: peer pick + loss per (hot node, round)
 };
 
 struct u32x4 { uint32_t x, y, z, w; };

@@ -1,0 +1,173 @@
+// gs_rumor_host.cpp -- the host side of rumor mongering (GS_MODEL_RUMOR,
+// DESIGN.md section 4.7): its buffers, the round loop and gs_run's stop rule.
+// One trial on one device; the kernels are in gs_rumor.hip.
+#include "gs_ctx.h"
+
+namespace gs {
+
+namespace {
+
+RumorState rumor_state(const gs_ctx* c) {
+  return RumorState{(RumorCtl*)c->rm.ctlb.p, c->d_next, (uint8_t*)c->rm.miss.p, c->p.rumor_k};
+}
+
+// The round's counters on the host: c's cumulative figures and its one
+// TrialAcc.  tick_99 is taken at polls only: `poll` says this tick is one.
+void rumor_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, bool poll, gs_tick_stats* o) {
+  c->t = tick;
+  c->fired += s[ST_FIRED];
+  c->sent += s[ST_SENT];
+  c->msgs += s[ST_MSGS];
+  c->recv += s[ST_RECV];
+  c->pending = s[ST_SCHED];  // the hot nodes after the round
+  TrialAcc& a = c->tacc[0];
+  a.fired = c->fired; a.sent = c->sent; a.msgs = c->msgs; a.recv = c->recv;
+  if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = tick;
+  if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
+}
+
+}  // namespace
+
+// The combinations the model does not run yet (a batched or sharded version
+// is the follow-up): the creates with more than one device or process.
+int rumor_refuse(const gs_params* params, const char* what) {
+  if (!params || params->model != GS_MODEL_RUMOR) return GS_OK;
+  g_create_err = std::string(what) + " with GS_MODEL_RUMOR: the rumor model runs one trial on one device (gs_create)";
+  fprintf(stderr, "%s: %s\n", what, g_create_err.c_str());
+  return GS_EINVAL;
+}
+
+// Nothing of the flood's window buffers or push-pull's reverse table: two
+// lists, the miss bytes and the control block.  At n = 1e9: 4 + 4 + 1 GB,
+// from the block cache like every buffer of 64 MiB or more.
+int rumor_alloc(gs_ctx* c) {
+  const uint64_t n = c->st.n;
+  if (!grow(c->rm.list[0], n * 4) || !grow(c->rm.list[1], n * 4) || !grow(c->rm.miss, n) ||
+      !grow(c->rm.ctlb, sizeof(RumorCtl)) || hipHostMalloc((void**)&c->rm.h_ctl, sizeof(RumorCtl)) != hipSuccess)
+    return fail(c, GS_ENOMEM, "cannot allocate the rumor model's hot lists");
+  return GS_OK;
+}
+
+// (removed grows at the first gs_read_removed)
+void release_rumor(gs_ctx* c) {
+  RumorBufs& b = c->rm;
+  for (Buf* q : {&b.list[0], &b.list[1], &b.miss, &b.ctlb, &b.removed}) release(*q);
+  if (b.h_ctl) (void)hipHostFree(b.h_ctl);
+}
+
+// The sender is informed unless failed (received = 1, as in push-pull) and
+// hot if it has a friend to call.
+int rumor_begin(gs_ctx* c, uint64_t sender) {
+  CK(c, hipSetDevice(c->dev));
+  // GS_RUMOR_GRID: the round kernel's blocks (read per broadcast, so tests can
+  // make a short list take several passes of the grid)
+  const char* e = getenv("GS_RUMOR_GRID");
+  c->rm.grid = rumor_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
+  c->rm.cur = 0;
+  CK(c, hipMemsetAsync(c->rm.ctlb.p, 0, sizeof(RumorCtl), c->stream));
+  CK(c, hipMemsetAsync(c->rm.miss.p, 0, c->st.n, c->stream));
+  CK(c, rumor_seed(c->st, rumor_state(c), (uint32_t*)c->rm.list[0].p, (uint32_t)sender, cover_threshold(c->p.n),
+                   c->stream));
+  CK(c, hipMemcpyAsync(c->rm.h_ctl, c->rm.ctlb.p, sizeof(RumorCtl), hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  c->recv = c->tacc[0].recv = c->rm.h_ctl->received;
+  c->pending = c->rm.h_ctl->rlen;
+  c->begun = true;
+  return GS_OK;
+}
+
+// `ticks` rounds, enqueued without a host sync between them; the stats rows
+// and the control block come back once per call (per kStatSlots rounds).
+// every_tick_polls: each tick is a poll (gs_step returns every tick's row);
+// else only the call's last tick is (gs_run).
+int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  CK(c, hipSetDevice(c->dev));
+  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
+  const RumorState rs = rumor_state(c);
+  uint32_t done = 0;
+  while (done < ticks) {
+    const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
+    const uint64_t t0 = c->t + 1;
+    const StatSpans sp = stat_spans(t0, batch);
+    while (timing && c->ev.size() < (size_t)batch * 3) {
+      hipEvent_t ev;
+      CK(c, hipEventCreate(&ev));
+      c->ev.push_back(ev);
+    }
+    for (uint32_t i = 0; i < batch; ++i) {
+      const uint32_t tt = (uint32_t)(t0 + i);
+      hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
+      if (ev) CK(c, hipEventRecord(ev[0], c->stream));
+      CK(c, rumor_round(c->st, rs, (const uint32_t*)c->rm.list[c->rm.cur].p, (uint32_t*)c->rm.list[c->rm.cur ^ 1].p, tt,
+                        c->rm.grid, c->stream));
+      if (ev) CK(c, hipEventRecord(ev[1], c->stream));
+      CK(c, rumor_commit(c->st, rs, tt, c->stream));
+      if (ev) CK(c, hipEventRecord(ev[2], c->stream));
+      c->rm.cur ^= 1;
+    }
+    for (int j = 0; j < sp.n; ++j)
+      CK(c, hipMemcpyAsync(c->h_stats + sp.off[j], c->st.stats + sp.off[j], sp.words[j] * 8, hipMemcpyDeviceToHost,
+                           c->stream));
+    CK(c, hipMemcpyAsync(c->rm.h_ctl, c->rm.ctlb.p, sizeof(RumorCtl), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < batch && timing; ++i) {
+      float ms = 0;
+      CK(c, hipEventElapsedTime(&ms, c->ev[(size_t)i * 3], c->ev[(size_t)i * 3 + 1]));
+      c->timing.deliver_ms += ms;  // the round kernel
+      c->timing.deliver_launches++;
+      CK(c, hipEventElapsedTime(&ms, c->ev[(size_t)i * 3 + 1], c->ev[(size_t)i * 3 + 2]));
+      c->timing.resolve_ms += ms;  // commit + publish
+      c->timing.resolve_launches++;
+    }
+    for (uint32_t i = 0; i < batch; ++i) {
+      const unsigned long long* s = c->h_stats + (size_t)((t0 + i) % kStatSlots) * kStatFields;
+      const bool poll = every_tick_polls || done + i + 1 == ticks;
+      rumor_account(c, t0 + i, s, poll, out ? &out[done + i] : nullptr);
+    }
+    if (c->rm.h_ctl->received != c->recv || c->rm.h_ctl->rlen != c->pending)
+      return fail(c, GS_EDEVICE, "the rumor control block and the stats rows disagree");
+    done += batch;
+  }
+  return GS_OK;
+}
+
+// The run goes to its own end: it stops at the first poll with no hot node
+// (the device's stop word: covered or quiescent by the float32 rule at that
+// poll), or at max_ticks.  Reaching 99 % does not stop it.
+int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+              int32_t* status) {
+  if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
+  size_t k = 0;
+  int32_t st = GS_RUN_MAX_TICKS;
+  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
+  for (;;) {
+    RC(rumor_step(c, poll, nullptr, false));
+    if (out && k < cap)
+      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
+    ++k;
+    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
+    if (c->rm.h_ctl->stop) { st = (int32_t)c->rm.h_ctl->stop - 1; break; }
+    if (c->t >= max_ticks) break;
+  }
+  snap_trial(c, 0, st);
+  if (nout) *nout = k;
+  if (status) *status = st;
+  return GS_OK;
+}
+
+// removed = informed and not hot: a copy of recv less the current list's nodes.
+int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
+  if (!c->rumor) return fail(c, GS_EINVAL, "gs_read_removed needs a GS_MODEL_RUMOR context");
+  if (!words || nwords < c->st.W) return fail(c, GS_EINVAL, "need ceil(n/64) words");
+  CK(c, hipSetDevice(c->dev));
+  if (!grow(c->rm.removed, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the removed set");
+  unsigned long long* d = (unsigned long long*)c->rm.removed.p;
+  CK(c, hipMemcpyAsync(d, c->st.recv, c->st.W * 8, hipMemcpyDeviceToDevice, c->stream));
+  if (c->begun)  // (before a broadcast recv is empty and the list is the last run's)
+    CK(c, rumor_removed(rumor_state(c), (const uint32_t*)c->rm.list[c->rm.cur].p, d, c->rm.grid, c->stream));
+  CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
+}  // namespace gs

@@ -35,7 +35,10 @@ class Config:
     device: int = 0
     timing: bool = False
     engine: str = "window"  # "window" (default) or "tick" (per-tick atomic engine)
-    model: str = "flood"    # "flood" (the reference) or "pushpull" (extension)
+    model: str = "flood"    # "flood" (the reference), "pushpull" (extension) or
+                            # "rumor" (extension, DESIGN.md 4.7: one trial, one device)
+    rumor_k: int = 2        # rumor: a node stops calling after this many calls that reached an
+                            # informed peer (1..255)
     trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3), either model
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
@@ -46,6 +49,7 @@ class Config:
                               # pull-answer)
 
     PP_ROUNDS = ("auto", "dense", "early", "topdown", "bottom", "answer")
+    MODELS = {"flood": _lib.GS_MODEL_FLOOD, "pushpull": _lib.GS_MODEL_PUSHPULL, "rumor": _lib.GS_MODEL_RUMOR}
 
     def flags(self, timing: bool | None = None) -> int:
         if self.pp_rounds not in self.PP_ROUNDS:
@@ -66,9 +70,13 @@ class Config:
         p.delay_low, p.delay_high = self.delaylow, self.delayhigh
         p.drop_rate, p.crash_rate = self.droprate, self.crashrate
         p.seed, p.trial, p.device = self.seed, self.trial, self.device
-        if self.model not in ("flood", "pushpull"):
-            raise ValueError(f"model must be 'flood' or 'pushpull', not {self.model!r}")
-        p.model = _lib.GS_MODEL_PUSHPULL if self.model == "pushpull" else _lib.GS_MODEL_FLOOD
+        if self.model not in self.MODELS:
+            raise ValueError(f"model must be 'flood', 'pushpull' or 'rumor', not {self.model!r}")
+        p.model = self.MODELS[self.model]
+        if self.model == "rumor":
+            if not 1 <= int(self.rumor_k) <= 255:
+                raise ValueError(f"rumor_k must be in 1..255, not {self.rumor_k!r}")
+            p.rumor_k = int(self.rumor_k)
         p.flags = self.flags()
         p.trials = max(1, int(self.trials))
         return p
@@ -281,6 +289,12 @@ class Simulator:
         w = np.zeros(self.words * self.trials, dtype=np.uint64)
         self._check(self.L.gs_read_crashed(self.h, w.ctypes.data, w.size), "gs_read_crashed")
         return w if self.trials == 1 else w.reshape(self.trials, self.words)
+
+    def removed(self) -> np.ndarray:
+        """Rumor model: the removed nodes (informed, no longer calling), ceil(n/64) words."""
+        w = np.zeros(self.words, dtype=np.uint64)
+        self._check(self.L.gs_read_removed(self.h, w.ctypes.data, w.size), "gs_read_removed")
+        return w
 
     def trial_results(self) -> np.ndarray:
         """[trials, len(TRIAL_FIELDS)] int64: per trial its number, first

@@ -69,6 +69,19 @@ enum {
                               * accepted and ignored (there is one round kind); gs_set_failed
                               * takes one mask per trial (a third bitset in LDS, so then
                               * n <= gs_pp_trials_max_n_masked()) */
+#define GS_MODEL_RUMOR 2u    /* extension, no reference counterpart: rumor mongering with loss of
+                              * interest (Demers et al.).  One synchronous round per tick; every HOT
+                              * node (informed, live, a friend to call, fewer than rumor_k misses)
+                              * calls one Philox-picked friend; a kept call to a live uninformed
+                              * friend informs it (hot from the next round), one to a friend that
+                              * was informed at the start of the round is a miss, and after
+                              * rumor_k misses the caller is REMOVED.  The run ends by itself when
+                              * no node is hot.  -droprate loses calls (no feedback either),
+                              * -delaylow/-delayhigh/-crashrate are unused, gs_set_failed masks
+                              * nodes (a failed callee gives no feedback).  gs_tick_stats.pending =
+                              * the hot nodes after the round.  One trial on one device: trials > 1,
+                              * gs_create_multi and gs_create_rank[_exchange] answer GS_EINVAL
+                              *  */
 
 /* simulator.go:11-20 (Parameters) + the additive -seed/-trial knobs. */
 typedef struct gs_params {
@@ -90,7 +103,8 @@ typedef struct gs_params {
    * Both models; trials << max(14, ceil(log2 n)) must be < 2^31.
    * The reference runs one trial per process (simulator.go:207-253). */
   uint32_t trials;
-  uint32_t reserved0_;
+  uint32_t rumor_k;    /* GS_MODEL_RUMOR: misses after which a node stops calling, 1..255
+                        * (the other models ignore it) */
   uint64_t reserved_[5];
 } gs_params;
 
@@ -294,7 +308,11 @@ int gs_step(gs_ctx* ctx, uint32_t ticks, gs_tick_stats* out);
  * informed node has a live uninformed friend and no live uninformed node has
  * an informed friend, or every call is dropped), or max_ticks.  out (may be
  * NULL) receives one gs_tick_stats per poll.  Batched trials: each trial
- * stops at its own poll (gs_trial_results); the run ends when all have. */
+ * stops at its own poll (gs_trial_results); the run ends when all have.
+ * GS_MODEL_RUMOR runs to its own end: it stops at the first poll with no hot
+ * node (pending == 0) -- GS_RUN_COVERED if the float32 rule holds at that poll,
+ * else GS_RUN_QUIESCENT -- or at max_ticks; reaching 99 % does not stop it, and
+ * gs_trial_stats.tick_99 is the first poll at which the rule held. */
 int gs_run(gs_ctx* ctx, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out,
            size_t cap, size_t* nout, int32_t* status);
 /* Cumulative totals so far (tick, fired/sent/messages summed). */
@@ -308,6 +326,10 @@ int gs_trial_results(gs_ctx* ctx, gs_trial_stats* out, size_t cap, size_t* nout)
  * multi-process run fills only the words of the nodes it owns (others 0). */
 int gs_read_received(gs_ctx* ctx, uint64_t* words, size_t nwords);
 int gs_read_crashed(gs_ctx* ctx, uint64_t* words, size_t nwords);
+/* GS_MODEL_RUMOR: the removed nodes -- informed and no longer hot (rumor_k
+ * misses, or no friend to call) -- in the same layout, words[ceil(n/64)].
+ * GS_EINVAL on a context of another model. */
+int gs_read_removed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 
 int gs_timing_get(gs_ctx* ctx, gs_timing* out);
 /* The same for shard `index` of a sharded (or batched) context's members;
