@@ -7,7 +7,8 @@ Layers:
   csrc/gs_window.hip        window engine: expand, partition, resolve (default)
   csrc/gs_pushpull.hip      push-pull rounds (extension, config C5)
   csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
-  csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set
+  csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set;
+                            the pull variants: a dense engine over bitsets
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI entry points: argument checks, dispatch by context kind
   csrc/gs_ctx.h, gs_ctx.cpp the context behind the ABI: set-up and release of every kind

@@ -24,6 +24,7 @@ GS_FLAG_PP_TOPDOWN = 32
 GS_FLAG_PP_BOTTOM = 64
 GS_FLAG_PP_ANSWER = 128
 GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR = 0, 1, 2
+GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL = 1, 2, 4
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
 GS_COMM_ID_BYTES = 128
 
@@ -63,7 +64,9 @@ class Params(C.Structure):
         ("model", C.c_uint32),  # GS_MODEL_FLOOD = 0 (reference), GS_MODEL_PUSHPULL = 1, GS_MODEL_RUMOR = 2
         ("trials", C.c_uint32),  # batched independent trials (config C3); 0/1 = one
         ("rumor_k", C.c_uint32),  # GS_MODEL_RUMOR: misses after which a node stops calling (1..255)
-        ("reserved_", C.c_uint64 * 5),
+        ("rumor_mode", C.c_uint32),  # GS_MODEL_RUMOR: GS_RUMOR_* bits (0 = push, feedback, counter)
+        ("reserved32_", C.c_uint32),
+        ("reserved_", C.c_uint64 * 4),
     ]
 
 

@@ -53,10 +53,10 @@ void usage() {  // flag.PrintDefaults, lexical order
   for (auto& kv : sorted) {
     Flag* f = kv.second;
     std::string b = std::string("  -") + f->name;
-    if (f->type[0]) b += std::string(" ") + f->type;
+    if (f->type[0] && strcmp(f->type, "bool")) b += std::string(" ") + f->type;  // Go names no type for a bool
     b += (b.size() <= 4) ? "\t" : "\n    \t";
     b += f->usage;
-    const bool zero = f->defv == "0" || f->defv.empty();
+    const bool zero = f->defv == "0" || f->defv.empty() || f->defv == "false";
     if (!zero) {
       if (!strcmp(f->type, "string")) b += " (default \"" + f->defv + "\")";
       else b += " (default " + f->defv + ")";
@@ -107,6 +107,10 @@ void parse(int argc, char** argv) {
       if (name == "h" || name == "help") { usage(); exit(0); }
       die_usage("flag provided but not defined: -" + name);
     }
+    if (!has && !strcmp(f->type, "bool")) {  // -name alone sets a bool; -name=false clears it
+      value = "true";
+      has = true;
+    }
     if (!has) {
       if (i + 1 >= argc) die_usage("flag needs an argument: -" + name);
       value = argv[++i];
@@ -121,6 +125,10 @@ void parse(int argc, char** argv) {
       if (!parse_float(value, v))
         die_usage("invalid value \"" + value + "\" for flag -" + name + ": parse error");
       f->val = gofloat(v);
+    } else if (!strcmp(f->type, "bool")) {
+      if (value != "true" && value != "false" && value != "1" && value != "0")
+        die_usage("invalid boolean value \"" + value + "\" for -" + name + ": parse error");
+      f->val = value == "true" || value == "1" ? "true" : "false";
     } else {
       f->val = value;
     }
@@ -198,6 +206,12 @@ int main(int argc, char** argv) {
        "flood", false, "flood"},
       {"k", "int", "rumor model: a node stops calling after this many calls that reached an informed peer",
        "2", false, "2"},
+      {"blind", "bool", "rumor model: a hot node loses interest without waiting for a reply (GS_RUMOR_BLIND)",
+       "false", false, "false"},
+      {"coin", "bool", "rumor model: lose interest with probability 1/k per event, not after k events (GS_RUMOR_COIN)",
+       "false", false, "false"},
+      {"pull", "bool", "rumor model: every node calls and hot nodes answer (GS_RUMOR_PULL)", "false", false,
+       "false"},
       {"maxticks", "int", "give up after this many simulated ms per phase", "10000000", false,
        "10000000"},
   };
@@ -213,6 +227,18 @@ int main(int argc, char** argv) {
     fprintf(stderr, "invalid value \"%s\" for flag -k: want 1..255\n", find("k")->val.c_str());
     usage();
     return 2;
+  }
+
+  uint32_t rumor_mode = 0;
+  for (const auto& fb : {std::make_pair("blind", GS_RUMOR_BLIND), std::make_pair("coin", GS_RUMOR_COIN),
+                         std::make_pair("pull", GS_RUMOR_PULL)}) {
+    if (find(fb.first)->val != "true") continue;
+    if (model != "rumor") {
+      fprintf(stderr, "flag -%s needs -model rumor (it selects a variant of the rumor model)\n", fb.first);
+      usage();
+      return 2;
+    }
+    rumor_mode |= fb.second;
   }
 
   printf("=== Parameters ===\n");                              // :197-204
@@ -239,7 +265,10 @@ int main(int argc, char** argv) {
   p.trial = (uint32_t)strtoull(find("trial")->val.c_str(), nullptr, 10);
   p.device = (int32_t)ival("device");
   p.model = model == "pushpull" ? GS_MODEL_PUSHPULL : model == "rumor" ? GS_MODEL_RUMOR : GS_MODEL_FLOOD;
-  if (p.model == GS_MODEL_RUMOR) p.rumor_k = (uint32_t)rumor_k;
+  if (p.model == GS_MODEL_RUMOR) {
+    p.rumor_k = (uint32_t)rumor_k;
+    p.rumor_mode = rumor_mode;
+  }
   const uint64_t max_ticks = (uint64_t)ival("maxticks");
   const long long ntrials = ival("trials");
   if (ntrials < 1 || ntrials > 0x7FFFFFFFll) {

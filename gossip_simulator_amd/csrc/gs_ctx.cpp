@@ -36,6 +36,11 @@ int check_params(const gs_params* p, std::string& why) {
     why = "GS_MODEL_RUMOR needs 1 <= rumor_k <= 255, not " + std::to_string(p->rumor_k);
     return GS_EINVAL;
   }
+  if (p->model == GS_MODEL_RUMOR && (p->rumor_mode & ~(GS_RUMOR_BLIND | GS_RUMOR_COIN | GS_RUMOR_PULL))) {
+    why = "GS_MODEL_RUMOR: rumor_mode " + std::to_string(p->rumor_mode) +
+          " has a bit that is none of GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL";
+    return GS_EINVAL;
+  }
   if (p->model == GS_MODEL_RUMOR && p->trials > 1) {
     why = "GS_MODEL_RUMOR with trials > 1: the rumor model runs one trial per context (batched trials are not built)";
     return GS_EINVAL;

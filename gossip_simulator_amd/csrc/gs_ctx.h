@@ -96,11 +96,12 @@ struct PpSparseBufs {
   unsigned long long cl_counts[2] = {0, 0};
 };
 
-// rumor mongering (gs_rumor.hip): the two hot lists [n] u32, the miss counts
-// [n] u8, round control (RumorCtl) and, once gs_read_removed asks, the removed
-// bitset [W]: rumor_alloc / release_rumor
+// rumor mongering (gs_rumor.hip): the two hot lists [n] u32 (push modes) or the
+// hot, served and vain bitsets [W] (pull modes), the miss counts [n] u8, round
+// control (RumorCtl) and, once gs_read_removed asks, the removed bitset [W]:
+// rumor_alloc / release_rumor
 struct RumorBufs {
-  Buf list[2], miss, ctlb, removed;
+  Buf list[2], hot, served, vain, miss, ctlb, removed;
   uint32_t cur = 0;   // list[cur] is the next round's read list
   uint32_t grid = 0;  // the round kernel's persistent grid (rumor_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll

@@ -513,6 +513,7 @@ hipError_t ppt_stalled(const PptState& s, const uint8_t* need, uint32_t* live, h
 // round (k_rumor_publish) and read by the next round's kernels.
 enum RumorAcc : uint32_t { RA_FIRED = 0, RA_SENT = 1, RA_MSGS = 2, RA_NEW = 3 };
 constexpr uint32_t kRumorCovered = 1, kRumorQuiescent = 2;  // RumorCtl::stop: 1 + GS_RUN_*
+constexpr uint32_t kRumorBlind = 1, kRumorCoin = 2, kRumorPull = 4;  // GS_RUMOR_* (gs_rumor_host.cpp asserts it)
 struct RumorCtl {
   unsigned long long wlen;      // entries appended to the write list this round
   unsigned long long pad0_[31];
@@ -531,6 +532,11 @@ struct RumorState {
   unsigned long long* next;     // [W] informed set being built
   uint8_t* miss;                // [n] kept calls that reached an informed peer; written by v's own lane only
   uint32_t k;                   // misses after which a node is removed (gs_params.rumor_k)
+  uint32_t mode;                // gs_params.rumor_mode (GS_RUMOR_*)
+  // the pull modes' dense engine (null in the push modes): no lists
+  unsigned long long* hot;      // [W] the hot set at the start of the round
+  unsigned long long* served;   // [W] hot nodes that informed a caller this round (zero between rounds)
+  unsigned long long* vain;     // [W] hot nodes an informed caller reached this round (zero between rounds)
 };
 // The persistent round grid for n nodes: `want` blocks (0: 256 CUs x 8), at most one lane per node.
 uint32_t rumor_grid(uint64_t n, uint32_t want);
@@ -545,6 +551,18 @@ hipError_t rumor_commit(const DevState& s, const RumorState& r, uint32_t t, hipS
 // out (holding a copy of recv) &= ~(the nodes of rlist): the removed set.
 hipError_t rumor_removed(const RumorState& r, const uint32_t* rlist, unsigned long long* out, uint32_t grid,
                          hipStream_t st);
+// The pull modes (GS_RUMOR_PULL): a dense engine over the bitsets of RumorState,
+// a wave per 64-node word.  ctl->rlen / wlen hold the hot count before / after
+// the round, so k_rumor_publish serves both engines.
+// ctl and the three bitsets zeroed by the caller; a live sender is informed and hot, friend or not.
+hipError_t rumor_pull_seed(const DevState& s, const RumorState& r, uint32_t node, unsigned long long cover,
+                           hipStream_t st);
+// Round t: every live node with a friend calls; next, served and vain are built from recv and hot.
+hipError_t rumor_pull_round(const DevState& s, const RumorState& r, uint32_t t, uint32_t grid, hipStream_t st);
+// The events of round t (miss counts, coins), the new hot set, recv = next, then the stats row as rumor_commit.
+hipError_t rumor_pull_commit(const DevState& s, const RumorState& r, uint32_t t, hipStream_t st);
+// out = recv & ~hot: the removed set.
+hipError_t rumor_pull_removed(const DevState& s, const RumorState& r, unsigned long long* out, hipStream_t st);
 
 // Launchers (gs_broadcast.hip).
 hipError_t launch_tick(const DevState& st, uint32_t tick, int mode, hipStream_t s);

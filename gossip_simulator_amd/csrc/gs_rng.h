@@ -16,6 +16,7 @@
 //   kind ORDER   simulator.go:107-115 ctr {u, t, (g-1)/4, .}    out[(g-1)%4] -> U_(k-g+1): receipt
 //                                   order, first_crash() below
 //   kind RUMOR (extension)           ctr {v, t, 0, .}            out[0] -> U_deg, out[1] -> U_100
+//                                   ctr {v, t, 1, .}            out[0] -> U_k: the coin of v's event
 // with counter word 3 = kind << 24 | trial.  U_m(r) = floor(r*m / 2^32).
 #pragma once
 #include <stdint.h>

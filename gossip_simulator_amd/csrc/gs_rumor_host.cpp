@@ -7,9 +7,16 @@ namespace gs {
 
 namespace {
 
+static_assert(kRumorBlind == GS_RUMOR_BLIND && kRumorCoin == GS_RUMOR_COIN && kRumorPull == GS_RUMOR_PULL,
+              "the kernels' mode bits are gossip.h's");
+
 RumorState rumor_state(const gs_ctx* c) {
-  return RumorState{(RumorCtl*)c->rm.ctlb.p, c->d_next, (uint8_t*)c->rm.miss.p, c->p.rumor_k};
+  return RumorState{(RumorCtl*)c->rm.ctlb.p, c->d_next, (uint8_t*)c->rm.miss.p, c->p.rumor_k, c->p.rumor_mode,
+                    (unsigned long long*)c->rm.hot.p, (unsigned long long*)c->rm.served.p,
+                    (unsigned long long*)c->rm.vain.p};
 }
+
+bool pull(const gs_ctx* c) { return (c->p.rumor_mode & GS_RUMOR_PULL) != 0; }
 
 // The round's counters on the host: c's cumulative figures and its one
 // TrialAcc.  tick_99 is taken at polls only: `poll` says this tick is one.
@@ -39,19 +46,25 @@ int rumor_refuse(const gs_params* params, const char* what) {
 
 // Nothing of the flood's window buffers or push-pull's reverse table: two
 // lists, the miss bytes and the control block.  At n = 1e9: 4 + 4 + 1 GB,
-// from the block cache like every buffer of 64 MiB or more.
+// from the block cache like every buffer of 64 MiB or more.  The pull modes
+// have three bitsets (3 x 125 MB) in place of the lists.
 int rumor_alloc(gs_ctx* c) {
   const uint64_t n = c->st.n;
-  if (!grow(c->rm.list[0], n * 4) || !grow(c->rm.list[1], n * 4) || !grow(c->rm.miss, n) ||
-      !grow(c->rm.ctlb, sizeof(RumorCtl)) || hipHostMalloc((void**)&c->rm.h_ctl, sizeof(RumorCtl)) != hipSuccess)
-    return fail(c, GS_ENOMEM, "cannot allocate the rumor model's hot lists");
+  const bool sets = pull(c);
+  if (sets ? !grow(c->rm.hot, c->st.W * 8) || !grow(c->rm.served, c->st.W * 8) || !grow(c->rm.vain, c->st.W * 8)
+           : !grow(c->rm.list[0], n * 4) || !grow(c->rm.list[1], n * 4))
+    return fail(c, GS_ENOMEM, sets ? "cannot allocate the rumor model's hot sets"
+                                   : "cannot allocate the rumor model's hot lists");
+  if (!grow(c->rm.miss, n) || !grow(c->rm.ctlb, sizeof(RumorCtl)) ||
+      hipHostMalloc((void**)&c->rm.h_ctl, sizeof(RumorCtl)) != hipSuccess)
+    return fail(c, GS_ENOMEM, "cannot allocate the rumor model's miss counts");
   return GS_OK;
 }
 
 // (removed grows at the first gs_read_removed)
 void release_rumor(gs_ctx* c) {
   RumorBufs& b = c->rm;
-  for (Buf* q : {&b.list[0], &b.list[1], &b.miss, &b.ctlb, &b.removed}) release(*q);
+  for (Buf* q : {&b.list[0], &b.list[1], &b.hot, &b.served, &b.vain, &b.miss, &b.ctlb, &b.removed}) release(*q);
   if (b.h_ctl) (void)hipHostFree(b.h_ctl);
 }
 
@@ -66,8 +79,13 @@ int rumor_begin(gs_ctx* c, uint64_t sender) {
   c->rm.cur = 0;
   CK(c, hipMemsetAsync(c->rm.ctlb.p, 0, sizeof(RumorCtl), c->stream));
   CK(c, hipMemsetAsync(c->rm.miss.p, 0, c->st.n, c->stream));
-  CK(c, rumor_seed(c->st, rumor_state(c), (uint32_t*)c->rm.list[0].p, (uint32_t)sender, cover_threshold(c->p.n),
-                   c->stream));
+  if (pull(c)) {  // a live sender is hot even with an empty row
+    for (Buf* q : {&c->rm.hot, &c->rm.served, &c->rm.vain}) CK(c, hipMemsetAsync(q->p, 0, c->st.W * 8, c->stream));
+    CK(c, rumor_pull_seed(c->st, rumor_state(c), (uint32_t)sender, cover_threshold(c->p.n), c->stream));
+  } else {
+    CK(c, rumor_seed(c->st, rumor_state(c), (uint32_t*)c->rm.list[0].p, (uint32_t)sender, cover_threshold(c->p.n),
+                     c->stream));
+  }
   CK(c, hipMemcpyAsync(c->rm.h_ctl, c->rm.ctlb.p, sizeof(RumorCtl), hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
   c->recv = c->tacc[0].recv = c->rm.h_ctl->received;
@@ -84,6 +102,7 @@ int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
   CK(c, hipSetDevice(c->dev));
   const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
   const RumorState rs = rumor_state(c);
+  const bool dense = pull(c);
   uint32_t done = 0;
   while (done < ticks) {
     const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
@@ -98,10 +117,13 @@ int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
       const uint32_t tt = (uint32_t)(t0 + i);
       hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
       if (ev) CK(c, hipEventRecord(ev[0], c->stream));
-      CK(c, rumor_round(c->st, rs, (const uint32_t*)c->rm.list[c->rm.cur].p, (uint32_t*)c->rm.list[c->rm.cur ^ 1].p, tt,
-                        c->rm.grid, c->stream));
+      if (dense)
+        CK(c, rumor_pull_round(c->st, rs, tt, c->rm.grid, c->stream));
+      else
+        CK(c, rumor_round(c->st, rs, (const uint32_t*)c->rm.list[c->rm.cur].p, (uint32_t*)c->rm.list[c->rm.cur ^ 1].p,
+                          tt, c->rm.grid, c->stream));
       if (ev) CK(c, hipEventRecord(ev[1], c->stream));
-      CK(c, rumor_commit(c->st, rs, tt, c->stream));
+      CK(c, dense ? rumor_pull_commit(c->st, rs, tt, c->stream) : rumor_commit(c->st, rs, tt, c->stream));
       if (ev) CK(c, hipEventRecord(ev[2], c->stream));
       c->rm.cur ^= 1;
     }
@@ -155,16 +177,21 @@ int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, 
   return GS_OK;
 }
 
-// removed = informed and not hot: a copy of recv less the current list's nodes.
+// removed = informed and not hot: a copy of recv less the current list's nodes
+// (the pull modes: recv & ~hot).
 int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   if (!c->rumor) return fail(c, GS_EINVAL, "gs_read_removed needs a GS_MODEL_RUMOR context");
   if (!words || nwords < c->st.W) return fail(c, GS_EINVAL, "need ceil(n/64) words");
   CK(c, hipSetDevice(c->dev));
   if (!grow(c->rm.removed, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the removed set");
   unsigned long long* d = (unsigned long long*)c->rm.removed.p;
-  CK(c, hipMemcpyAsync(d, c->st.recv, c->st.W * 8, hipMemcpyDeviceToDevice, c->stream));
-  if (c->begun)  // (before a broadcast recv is empty and the list is the last run's)
-    CK(c, rumor_removed(rumor_state(c), (const uint32_t*)c->rm.list[c->rm.cur].p, d, c->rm.grid, c->stream));
+  if (pull(c)) {  // every word written by the kernel (before a broadcast recv is empty)
+    CK(c, rumor_pull_removed(c->st, rumor_state(c), d, c->stream));
+  } else {
+    CK(c, hipMemcpyAsync(d, c->st.recv, c->st.W * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (c->begun)  // (before a broadcast recv is empty and the list is the last run's)
+      CK(c, rumor_removed(rumor_state(c), (const uint32_t*)c->rm.list[c->rm.cur].p, d, c->rm.grid, c->stream));
+  }
   CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
   return GS_OK;

@@ -39,6 +39,9 @@ class Config:
                             # "rumor" (extension, DESIGN.md 4.7: one trial, one device)
     rumor_k: int = 2        # rumor: a node stops calling after this many calls that reached an
                             # informed peer (1..255)
+    rumor_blind: bool = False  # rumor: an event every round a node is hot, reply or not (GS_RUMOR_BLIND)
+    rumor_coin: bool = False   # rumor: an event removes with probability 1/rumor_k (GS_RUMOR_COIN)
+    rumor_pull: bool = False   # rumor: every live node calls; hot nodes answer (GS_RUMOR_PULL)
     trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3), either model
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
@@ -77,6 +80,9 @@ class Config:
             if not 1 <= int(self.rumor_k) <= 255:
                 raise ValueError(f"rumor_k must be in 1..255, not {self.rumor_k!r}")
             p.rumor_k = int(self.rumor_k)
+            p.rumor_mode = (_lib.GS_RUMOR_BLIND if self.rumor_blind else 0) | \
+                (_lib.GS_RUMOR_COIN if self.rumor_coin else 0) | \
+                (_lib.GS_RUMOR_PULL if self.rumor_pull else 0)
         p.flags = self.flags()
         p.trials = max(1, int(self.trials))
         return p

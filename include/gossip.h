@@ -81,7 +81,23 @@ enum {
                               * nodes (a failed callee gives no feedback).  gs_tick_stats.pending =
                               * the hot nodes after the round.  One trial on one device: trials > 1,
                               * gs_create_multi and gs_create_rank[_exchange] answer GS_EINVAL
-                              *  */
+                              * (DESIGN.md section 4.7).  gs_params.rumor_mode (GS_RUMOR_*)
+                              * selects the other variants of Demers et al.; 0 is the model
+                              * above */
+
+/* Variants of GS_MODEL_RUMOR (gs_params.rumor_mode, any combination; the other
+ * models ignore the field; another bit answers GS_EINVAL). */
+#define GS_RUMOR_BLIND 1u /* a hot node has an event every round it is hot, reply or not (a lost
+                           * call and a failed callee count too), instead of only when its call
+                           * reached an informed peer */
+#define GS_RUMOR_COIN 2u  /* an event removes the node with probability 1/rumor_k (a keyed draw)
+                           * instead of after rumor_k events; the miss counts stay 0 */
+#define GS_RUMOR_PULL 4u  /* every live node with a friend calls every round; a call that reaches
+                           * a hot node informs an uninformed caller (the hot node was served) or
+                           * was in vain; a hot node's event: asked in vain and not served in the
+                           * round (feedback), or every round (blind).  Hot needs no friend here.
+                           * A hot node that no live node ever calls stays hot with feedback, so
+                           * such a run ends GS_RUN_MAX_TICKS */
 
 /* simulator.go:11-20 (Parameters) + the additive -seed/-trial knobs. */
 typedef struct gs_params {
@@ -105,7 +121,10 @@ typedef struct gs_params {
   uint32_t trials;
   uint32_t rumor_k;    /* GS_MODEL_RUMOR: misses after which a node stops calling, 1..255
                         * (the other models ignore it) */
-  uint64_t reserved_[5];
+  uint32_t rumor_mode; /* GS_MODEL_RUMOR: GS_RUMOR_* bits, 0 = push with feedback and counter
+                        * (the other models ignore it) */
+  uint32_t reserved32_;
+  uint64_t reserved_[4];
 } gs_params;
 
 /* One tick (1 ms) of the broadcast phase; the reference exposes these as the
@@ -327,7 +346,9 @@ int gs_trial_results(gs_ctx* ctx, gs_trial_stats* out, size_t cap, size_t* nout)
 int gs_read_received(gs_ctx* ctx, uint64_t* words, size_t nwords);
 int gs_read_crashed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 /* GS_MODEL_RUMOR: the removed nodes -- informed and no longer hot (rumor_k
- * misses, or no friend to call) -- in the same layout, words[ceil(n/64)].
+ * events or a lost coin toss, or in the push modes no friend to call; with
+ * GS_RUMOR_PULL an informed live node with no friend is hot, not removed) --
+ * in the same layout, words[ceil(n/64)].
  * GS_EINVAL on a context of another model. */
 int gs_read_removed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 
