@@ -4,7 +4,9 @@ go-distributed/gossip_simulator (simulator.go).
 Layers:
   include/gossip.h          C ABI (the drop-in seam; cgo binding in INTEGRATION.md)
   csrc/gs_broadcast.hip     tick kernels: delivery, infection, crash, stats
-  csrc/gs_window.hip        window engine: expand, partition, resolve (default)
+  csrc/gs_win_*.hip         window engine (default), one file per stage: units, expand,
+                            part (partition), resolve, shard; shared helpers in gs_win_dev.h
+  csrc/gs_wave.h            wave and block primitives shared by the kernels
   csrc/gs_pushpull.hip      push-pull rounds (extension, config C5)
   csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
   csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set;

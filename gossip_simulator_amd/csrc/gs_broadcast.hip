@@ -24,14 +24,9 @@
 // keyed crash rolls.  With crash% == 0 the FLOOD pass fuses delivery and
 // infection into one atomicOr per delivered send.
 #include "gs_internal.h"
+#include "gs_wave.h"
 
 namespace gs {
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Node.Broadcast() for node u infected at tick t: one delay per call
 // (simulator.go:141-142), a fire bit in ring slot (t+off) mod R, and the
@@ -105,7 +100,7 @@ __device__ __forceinline__ void process_chunk(const DevState& st, uint32_t t, ui
       list[pos++] = node0 + (uint32_t)__builtin_ctzll(bits);
       bits &= bits - 1;
     }
-    wave_sync();
+    wave_lds_sync();
     const uint32_t L = total < kListCap ? total : kListCap;
     const uint32_t tasks = L * S;
     for (uint32_t q = lane; q < tasks; q += kWave) {
@@ -144,7 +139,7 @@ __device__ __forceinline__ void process_chunk(const DevState& st, uint32_t t, ui
         if (k) resolve_node(st, u, k & 0xFFFFu, k >> 16, t, c);
       }
     }
-    wave_sync();
+    wave_lds_sync();
   }
 }
 

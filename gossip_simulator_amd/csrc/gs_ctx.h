@@ -36,7 +36,7 @@ struct TrialAcc {
   gs_trial_stats snap{};
 };
 
-// window engine (gs_window.hip): alloc_window / release_window
+// window engine (gs_win_*.hip): alloc_window / release_window
 struct WinEngine {
   void* d_win = nullptr;      // fcount + small per-window buffers
   void* d_flist = nullptr;    // [R][nfine][16384] u16
@@ -206,7 +206,7 @@ struct gs_ctx {
   // rumor mongering (gs_rumor.hip; d_next is its informed set being built)
   bool rumor = false;
   gs::RumorBufs rm;
-  // window engine (gs_window.hip)
+  // window engine (gs_win_*.hip)
   bool win = false;
   gs::WinState ws{};
   gs::WinEngine wn;

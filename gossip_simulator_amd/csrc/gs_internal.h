@@ -82,7 +82,7 @@ struct DevState {
   Key key;
 };
 
-// ---- window engine (gs_window.hip) --------------------------------------
+// ---- window engine (gs_win_*.hip, gs_win_dev.h) --------------------------
 // Fires scheduled at tick t land at t + off with off >= max(delaylow, 1), so
 // the firing sets of the next L = min(max(delaylow,1), 16) ticks are known
 // before any of them is processed: a WINDOW of L ticks is expanded,

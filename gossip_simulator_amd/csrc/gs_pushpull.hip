@@ -31,17 +31,12 @@
 
 #include "gs_internal.h"
 #include "gs_rev_plan.h"
+#include "gs_wave.h"
 
 namespace gs {
 namespace {
 
 constexpr uint32_t kPPBlock = 256;
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (uint32_t o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Per-block sums of up to 3 counters into stats[slot][f0..], one atomic each.
 template <uint32_t B = kPPBlock>
@@ -226,12 +221,6 @@ constexpr uint32_t kPPEdges = 4;    // in-edges loaded per batch
 constexpr uint32_t kPPSBlock = GS_PPS_BLOCK;  // k_ppb_round / k_ppa_round workgroup
 constexpr uint32_t kPPWaves = kPPSBlock / 64;
 constexpr uint32_t kPPSGrid = 512 * 1024 / kPPSBlock;  // at most 8192 waves per launch
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Position of the k-th set bit of m (k < popc(m)).
 __device__ __forceinline__ uint32_t nth_bit(unsigned long long m, uint32_t k) {

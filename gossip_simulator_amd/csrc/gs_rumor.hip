@@ -31,17 +31,12 @@
 // every live node call and the hot nodes answer: a dense engine over bitsets
 // (hot, served, vain) at the end of this file, with no lists.
 #include "gs_internal.h"
+#include "gs_wave.h"
 
 namespace gs {
 namespace {
 
 constexpr uint32_t kRmBlock = 256;
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (uint32_t o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Per-block sums of nf <= 3 counters into acc[0..nf), one atomic each.
 __device__ __forceinline__ void block_add(uint64_t* sh, const uint64_t (&v)[3], uint32_t nf,
@@ -59,11 +54,6 @@ __device__ __forceinline__ void block_add(uint64_t* sh, const uint64_t (&v)[3], 
     for (uint32_t k = 0; k < kRmBlock / 64; ++k) s += sh[tid * (kRmBlock / 64) + k];
     if (s) atomicAdd(&acc[tid], (unsigned long long)s);
   }
-}
-
-// Lanes below this one whose bit is set in the ballot b.
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long b) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
 }
 
 // The sender is informed unless failed, and hot if it has a friend.

@@ -32,7 +32,7 @@ void plan_coarse(gs_ctx* c, uint64_t T, const unsigned long long* exact) {
 // Batched trials (trials > 1, tlog <= kCoarseShift): a message never leaves
 // its sender's trial, so it lands in the sender's coarse bin, and the
 // sub-region it goes to is the XCD whose rounds expanded the sender
-// (xcd_rounds in gs_window.hip).  fb[b] = the first firing index of bin b
+// (xcd_rounds in gs_win_expand.hip).  fb[b] = the first firing index of bin b
 // (bins are contiguous in the bucket-major unit order), fb[ncoarse] = Tn.
 // Region (b, x) gets an exact upper bound -- the window's firing nodes of bin
 // b in XCD x's rounds, times the row length -- so it never overflows: the
@@ -64,7 +64,7 @@ void plan_coarse_trials(gs_ctx* c, const unsigned long long* fb, unsigned long l
 }
 
 // Window engine: ticks [t0, t0 + n) as windows of <= min(max(delaylow,1),10)
-// ticks (gs_window.hip).  One host sync per window reads its task count.
+// ticks (gs_win_*.hip).  One host sync per window reads its task count.
 int run_windows(gs_ctx* c, uint64_t t0, uint32_t n, bool timing, uint64_t tchunk) {
   RC(expand_view(c));
   WinState& w = c->ws;

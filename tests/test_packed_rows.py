@@ -1,4 +1,4 @@
-"""k_expand's packed row view (gs_window.hip pk_byte, k_pack_rows): row v of
+"""k_expand's packed row view (gs_win_expand.hip pk_byte, k_pack_rows): row v of
 a stride-8 sealed table lives at byte 128 * (v / 5) + 24 * (v mod 5), with v / 5
 computed as (v * 0xCCCCCCCD) >> 34, and is read as two 16-B loads from the
 row's 16-B aligned base.  CPU restatement of the index arithmetic and the

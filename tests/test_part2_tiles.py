@@ -1,4 +1,4 @@
-"""k_part2's tiles dealt by XCD (gs_window.hip tiles_by_xcd): k_plan writes
+"""k_part2's tiles dealt by XCD (gs_win_dev.h tiles_by_xcd): k_plan writes
 the tile prefix in the order (bin & 7, bin >> 3, sub-region); workgroup b of a
 grid that is a multiple of 8 takes XCD b & 7's run of tiles, strided by
 grid / 8.  CPU restatement: every tile of every region is taken exactly once,
