@@ -7,7 +7,9 @@ Layers:
   csrc/gs_win_*.hip         window engine (default), one file per stage: units, expand,
                             part (partition), resolve, shard; shared helpers in gs_win_dev.h
   csrc/gs_wave.h            wave and block primitives shared by the kernels
-  csrc/gs_pushpull.hip      push-pull rounds (extension, config C5)
+  csrc/gs_pp_*.hip          push-pull rounds (extension, config C5), one file per round mode or
+                            preparation step: dense, early, round, defer, rev (reverse table), fmask;
+                            what they share in gs_pp_dev.h
   csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
   csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set;
                             the pull variants: a dense engine over bitsets

@@ -195,7 +195,7 @@ struct gs_ctx {
   uint64_t t = 0, fired = 0, sent = 0, msgs = 0, recv = 0, crashed = 0, pending = 0;
   std::vector<hipEvent_t> ev;
   gs_timing timing{};
-  // push-pull extension (gs_pushpull.hip)
+  // push-pull extension (gs_pp_*.hip)
   bool pp = false, pp_l2_only = false;
   unsigned long long* d_next = nullptr;  // informed set being built (state block)
   unsigned long long* d_ppsum = nullptr;  // push-pull word summaries (state block)

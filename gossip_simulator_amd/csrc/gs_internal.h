@@ -19,12 +19,19 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "gs_devmem.h"
 #include "gs_rng.h"
 
 namespace gs {
+
+// Grid of a launch over `items` at per_block items a block, at most cap blocks.
+// No items: 0 -- a launcher whose kernel must still run asks for 1 itself.
+inline uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t cap) {
+  return (uint32_t)std::min<uint64_t>((items + per_block - 1) / per_block, cap);
+}
 
 constexpr uint32_t kWave = 64;
 constexpr uint32_t kChunkNodesLog = 12;  // 4096 nodes = 64 words per chunk
@@ -320,7 +327,8 @@ hipError_t win_pack(const WinState& w, const unsigned long long* poff, uint32_t 
 hipError_t win_schedule(const WinState& w, uint32_t node, uint32_t tick, uint32_t trials, uint32_t n,
                         hipStream_t s, uint32_t* started = nullptr);
 
-// Push-pull extension (gs_pushpull.hip): one round per tick; `next` is the
+// Push-pull extension (gs_pp_*.hip, a file per round mode: gs_pp_dev.h lists
+// them): one round per tick; `next` is the
 // informed set being built (equal to recv at the start of every round).
 // sum = pp_summary_total_words(W) words: the round's word summaries, one bit
 // per 64-node word (A: any informed, B: any live uninformed) and a second

@@ -7,7 +7,7 @@
 // global atomic and no launch per round: the words are loaded from the
 // context's recv bitset once, the rounds run between workgroup barriers, and
 // the words are stored back.  Draws, outcomes and counters are those of
-// k_pp_round (gs_pushpull.hip), keyed by the trial's own number: trial i of
+// k_pp_round (gs_pp_round.hip), keyed by the trial's own number: trial i of
 // the batch is a one-trial context with params.trial + i and, when the batch
 // has failure masks, trial i's mask (the kMasked instantiation below).
 //

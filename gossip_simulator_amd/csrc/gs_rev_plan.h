@@ -1,5 +1,5 @@
 // gs_rev_plan.h -- the pass plan of the partitioned reverse-table build
-// (pp_rev_build_part, gs_pushpull.hip).  Pure host arithmetic and no HIP
+// (pp_rev_build_part, gs_pp_rev.hip).  Pure host arithmetic and no HIP
 // header, so a host compiler takes it alone (tests/devmem_harness.cpp).
 //
 // The coarse bins are taken in passes of consecutive bins.  A pass holds two

@@ -43,18 +43,25 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Inclusive scan over the wave's 64 lanes: lane l gets the sum of lanes 0..l.
+template <class T>
+__device__ __forceinline__ T wave_inscan(T x) {
+  const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
 // Exclusive scan of one u64 per thread over a block of NW waves (s: NW words
 // of LDS); returns the thread's prefix, *total the block's sum.  Block-uniform.
 template <uint32_t NW>
 __device__ __forceinline__ unsigned long long block_exscan_u64(unsigned long long v, unsigned long long* s,
                                                                unsigned long long* total) {
+  const unsigned long long x = wave_inscan(v);
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned long long x = v;
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
   if (lane == 63) s[wv] = x;
   __syncthreads();
   unsigned long long before = 0, all = 0;

@@ -139,12 +139,7 @@ __device__ __forceinline__ void block_scan256(uint32_t* cnt, uint32_t* off) {
     const uint32_t l = threadIdx.x;
     const uint32_t a = cnt[4 * l], b = cnt[4 * l + 1], c = cnt[4 * l + 2], d = cnt[4 * l + 3];
     const uint32_t sum = a + b + c + d;
-    uint32_t x = sum;
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o, 64);
-      if (l >= o) x += y;
-    }
+    const uint32_t x = wave_inscan(sum);
     const uint32_t ex = x - sum;
     off[4 * l] = ex;
     off[4 * l + 1] = ex + a;

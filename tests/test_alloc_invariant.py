@@ -62,7 +62,8 @@ def test_product_never_uses_the_stream_ordered_pool():
 def test_the_scan_sees_every_product_source():
     names = {os.path.basename(p) for p in _sources()}
     for must in ("gs_overlay.hip", "gs_win_units.hip", "gs_win_expand.hip", "gs_win_part.hip", "gs_win_resolve.hip",
-                 "gs_win_shard.hip", "gs_win_dev.h", "gs_wave.h", "gs_pushpull.hip", "gs_api.cpp", "gossip.h", "gs_ctx.h",
+                 "gs_win_shard.hip", "gs_win_dev.h", "gs_wave.h", "gs_pp_dev.h", "gs_pp_dense.hip", "gs_pp_early.hip",
+                 "gs_pp_round.hip", "gs_pp_defer.hip", "gs_pp_rev.hip", "gs_pp_fmask.hip", "gs_api.cpp", "gossip.h", "gs_ctx.h",
                  "gs_ctx.cpp", "gs_peers.cpp", "gs_windows.cpp", "gs_shards.cpp", "gs_pushpull_host.cpp"):
         assert must in names
 

@@ -2,7 +2,7 @@
 (simulator.go only floods, :140-149), so the CPU restatement in
 oracle/gsoracle.c (pushpull_step) is pinned here by a second, independent
 pure-Python restatement and by hand-derived answers, and the HIP rounds
-(gs_pushpull.hip) must match it bit-exactly per round.
+(gs_pp_*.hip) must match it bit-exactly per round.
 """
 from __future__ import annotations
 

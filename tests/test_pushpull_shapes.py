@@ -1,4 +1,4 @@
-"""Push-pull parity sweep of the one-trial engine (gs_pushpull.hip): round
+"""Push-pull parity sweep of the one-trial engine (gs_pp_*.hip): round
 paths, slot widths, region boundaries, caps, hubs and row content.
 
 The engine picks its code from the row stride (packed slot bytes up to 16
