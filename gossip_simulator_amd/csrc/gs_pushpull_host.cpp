@@ -350,11 +350,16 @@ int pp_shard_begin(gs_ctx* acc, uint64_t sender) {
   // shards over several devices of one group run bottom-up only
   const bool onedev = !acc->group || acc->gr.devs.size() == 1;
   bool answer = onedev && !getenv("GS_PP_SHARD_BOTTOM") && (!acc->xc.has_hx || acc->xc.hx.all_to_allv);
+  // (pp_prepare builds a masked shard's fmask: the answer test reads it after every shard prepared --
+  // read before, the first broadcast after gs_set_failed found none and ran bottom-up only)
+  for (gs_ctx* m : ms) {
+    CK(m, hipSetDevice(m->dev));
+    if (int rc = pp_prepare(m)) return fail(acc, rc, m->err);
+  }
   for (gs_ctx* m : ms) answer = answer && m->rs.d_gn && (!m->failed || m->sp.fmask);
   acc->rs.pp_answer = answer;
   for (gs_ctx* m : ms) {
     CK(m, hipSetDevice(m->dev));
-    if (int rc = pp_prepare(m)) return fail(acc, rc, m->err);
     const uint32_t node = sender >= m->lo && sender < m->hi ? (uint32_t)(sender - m->lo) : ~0u;
     RC(pp_seed_ctx(m, m->d_next, node, 0ull, 0ull, ~0ull));
     uint32_t ok = 0;
