@@ -13,6 +13,8 @@ Layers:
   csrc/gs_pushpull_trials.hip  batched push-pull trials: a workgroup per trial, state in LDS
   csrc/gs_rumor.hip         rumor mongering rounds (extension): a list engine over the hot set;
                             the pull variants: a dense engine over bitsets
+  csrc/gs_rumor_trials.hip  batched rumor trials: a workgroup per trial, state in LDS, every mode
+                            dense over bitsets (plan: gs_rmt_plan.h)
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI entry points: argument checks, dispatch by context kind
   csrc/gs_ctx.h, gs_ctx.cpp the context behind the ABI: set-up and release of every kind
@@ -30,8 +32,8 @@ Layers:
 from ._lib import (GS_RUN_COVERED, GS_RUN_MAX_TICKS, GS_RUN_QUIESCENT,  # noqa: F401
                    GossipError, load)
 from .engine import (Config, Simulator, covered, memory_stats, pp_trials_max_n,  # noqa: F401
-                     pp_trials_max_n_masked, trim)
+                     pp_trials_max_n_masked, rumor_trials_max_n, trim)
 
 __all__ = ["Config", "Simulator", "GossipError", "covered", "load", "trim", "memory_stats", "pp_trials_max_n",
-           "pp_trials_max_n_masked", "GS_RUN_COVERED",
+           "pp_trials_max_n_masked", "rumor_trials_max_n", "GS_RUN_COVERED",
            "GS_RUN_QUIESCENT", "GS_RUN_MAX_TICKS"]

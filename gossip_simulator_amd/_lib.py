@@ -39,6 +39,7 @@ EXPORTS = (
     "gs_create_rank", "gs_shard_info", "gs_trial_results", "gs_set_trial",
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
     "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
+    "gs_create_trials", "gs_rumor_trials_max_n",
 )
 
 
@@ -130,6 +131,7 @@ def load():
         "gs_version": ([], C.c_int),
         "gs_strerror": ([C.c_int], C.c_char_p),
         "gs_create": ([P(Params), P(vp)], C.c_int),
+        "gs_create_trials": ([P(Params), P(vp)], C.c_int),
         "gs_destroy": ([ctx], None),
         "gs_last_error": ([ctx], C.c_char_p),
         "gs_load_peers": ([ctx, vp, vp, C.c_uint32], C.c_int),
@@ -165,6 +167,7 @@ def load():
         "gs_memory_stats": ([P(Timing)], C.c_int),
         "gs_pp_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_pp_trials_max_n_masked": ([C.c_int, P(C.c_uint64)], C.c_int),
+        "gs_rumor_trials_max_n": ([C.c_int, C.c_uint32, P(C.c_uint64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

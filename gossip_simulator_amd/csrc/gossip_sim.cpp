@@ -7,7 +7,11 @@
 // (-seed -trial -trials -device -peers -maxticks -model -k) are not echoed in
 // the parameter block, so stdout keeps the reference's shape.  -model rumor
 // runs to its own end and adds the residue and the messages per node.  -trials T > 1 runs
-// T independent trials in one batched context and prints one line per trial.
+// T independent trials in one batched context and prints one line per trial;
+// with -model rumor (gs_create_trials) the trial lines carry the model's own
+// figures and a summary line their mean and sample standard deviation, and
+// the exit status is 0 if every trial ended by itself (covered or quiescent),
+// 3 if one reached -maxticks.
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -288,10 +292,15 @@ int main(int argc, char** argv) {
     std::vector<int> devs;
     for (int64_t i = 0; i < gpus; ++i) devs.push_back((int)(p.device + i));
     rc = gs_create_multi(&p, devs.data(), (int)gpus, &c);
+  } else if (p.model == GS_MODEL_RUMOR && p.trials > 1) {
+    rc = gs_create_trials(&p, &c);  // gs_create keeps refusing the combination
   } else {
     rc = gs_create(&p, &c);
   }
-  if (rc) return die(nullptr, rc, "gs_create");
+  if (rc) {
+    fprintf(stderr, "%s: gs_create failed: %s (%s)\n", g_prog, gs_strerror(rc), gs_last_error(nullptr));
+    return 1;
+  }
 
   printf("\n=== Constructing Overlay ===\n");                   // :219
   const auto w0 = std::chrono::steady_clock::now();
@@ -340,6 +349,39 @@ int main(int argc, char** argv) {
     rc = gs_trial_results(c, tr.data(), tr.size(), &ntr);
     if (rc) return die(c, rc, "gs_trial_results");
     uint32_t got99 = 0;
+    if (p.model == GS_MODEL_RUMOR) {  // the model's own outputs per trial, then their statistics
+      static const char* const names[] = {"covered", "quiescent", "maxticks"};
+      const size_t T = std::min(ntr, tr.size());
+      double sum[3] = {0, 0, 0}, sq[3] = {0, 0, 0};
+      uint32_t ended = 0;
+      for (size_t i = 0; i < T; ++i) {
+        char rb[64], mb[64];
+        gs_format_float32(1.0f - (float)tr[i].received / (float)p.n, rb, sizeof(rb));
+        gs_format_float32((float)tr[i].messages / (float)p.n, mb, sizeof(mb));
+        printf("trial %" PRIu64 ": Residue %s, %s messages per node after %s, %s\n", tr[i].trial, rb, mb,
+               dur_ms(tr[i].tick).c_str(), names[tr[i].status >= 0 && tr[i].status <= 2 ? tr[i].status : 2]);
+        const double x[3] = {1.0 - (double)tr[i].received / (double)p.n, (double)tr[i].messages / (double)p.n,
+                             (double)tr[i].tick};
+        for (int f = 0; f < 3; ++f) sum[f] += x[f];
+        if (tr[i].status != GS_RUN_MAX_TICKS) ++ended;
+      }
+      double mean[3], sd[3];
+      for (int f = 0; f < 3; ++f) mean[f] = T ? sum[f] / (double)T : 0.0;
+      for (size_t i = 0; i < T; ++i) {  // two passes: the deviations from the mean
+        const double x[3] = {1.0 - (double)tr[i].received / (double)p.n, (double)tr[i].messages / (double)p.n,
+                             (double)tr[i].tick};
+        for (int f = 0; f < 3; ++f) sq[f] += (x[f] - mean[f]) * (x[f] - mean[f]);
+      }
+      for (int f = 0; f < 3; ++f) sd[f] = T > 1 ? std::sqrt(sq[f] / (double)(T - 1)) : 0.0;
+      printf("--- %zu trials: residue mean %s sd %s, messages per node mean %s sd %s, rounds mean %s sd %s ---\n", T,
+             gofloat(mean[0]).c_str(), gofloat(sd[0]).c_str(), gofloat(mean[1]).c_str(), gofloat(sd[1]).c_str(),
+             gofloat(mean[2]).c_str(), gofloat(sd[2]).c_str());
+      fflush(stdout);
+      const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
+      fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, %u broadcasts %.3f s\n", ov_wall, p.trials, wall);
+      gs_destroy(c);
+      return ended == T ? 0 : 3;
+    }
     for (size_t i = 0; i < ntr && i < tr.size(); ++i) {
       const float percent = (float)tr[i].received / (float)p.n;
       char pb[64];

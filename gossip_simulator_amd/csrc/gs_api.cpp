@@ -6,7 +6,8 @@
 //   plain    one device, one stream, one trial (window / tick / push-pull engine)
 //   batched  one device, `trials` independent trials laid out at trial << tlog
 //            and run at once (config C3): the flood model by the window engine,
-//            push-pull by the trial-resident kernel (a workgroup per trial)
+//            push-pull by the trial-resident kernel (a workgroup per trial), the
+//            rumor model by its own (gs_create_trials only)
 //   shard    one node range [lo, hi) of one broadcast (config C4): a member of a
 //            group, or one rank of a multi-process run (RCCL inside)
 //   group    gs_create_multi: shards or trial batches over several devices
@@ -180,6 +181,45 @@ int gs_create(const gs_params* params, gs_ctx** out) {
   if (!out) return GS_EINVAL;
   *out = nullptr;
   return create_one(params, params ? params->device : 0, false, 1, 0, out);
+}
+
+// gs_create with the rumor / trials refusal lifted: every other check of the
+// parameters still runs before any device call.
+int gs_create_trials(const gs_params* params, gs_ctx** out) {
+  g_create_err.clear();
+  if (!out) return GS_EINVAL;
+  *out = nullptr;
+  return create_one(params, params ? params->device : 0, false, 1, 0, out, true);
+}
+
+int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max) {
+  g_create_err.clear();
+  if (!n_max) return GS_EINVAL;
+  *n_max = 0;
+  int ndev = 0;
+  int rc = GS_EDEVICE;
+  std::string why;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (rumor_mode & ~(GS_RUMOR_BLIND | GS_RUMOR_COIN | GS_RUMOR_PULL)) {
+    why = "rumor_mode " + std::to_string(rumor_mode) + " has a bit that is none of GS_RUMOR_BLIND, GS_RUMOR_COIN, "
+          "GS_RUMOR_PULL";
+    rc = GS_EINVAL;
+  } else if (ce != hipSuccess) {
+    why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
+  } else if (device < 0 || device >= ndev) {
+    why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
+  } else {
+    uint64_t lim = 0;
+    why = rmt_limit_error(device, rumor_mode, &lim);
+    if (why.empty()) {
+      *n_max = rmt_max_n(rumor_mode, lim);
+      return GS_OK;
+    }
+  }
+  (void)hipGetLastError();
+  fprintf(stderr, "gs_rumor_trials_max_n: %s\n", why.c_str());
+  g_create_err = why;
+  return rc;
 }
 
 int gs_create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out) {

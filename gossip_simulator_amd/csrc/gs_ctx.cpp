@@ -15,7 +15,7 @@ uint32_t ceil_log2(uint64_t x) {
   return b;
 }
 
-int check_params(const gs_params* p, std::string& why) {
+int check_params(const gs_params* p, bool rumor_trials, std::string& why) {
   if (!p) { why = "params is NULL"; return GS_EINVAL; }
   if (p->n == 0) { why = "n must be >= 1 (simulator.go:240 panics on rand.Intn(0))"; return GS_EINVAL; }
   if (p->n > 0x7FFFFFFFull) { why = "n must be < 2^31"; return GS_EINVAL; }
@@ -41,8 +41,8 @@ int check_params(const gs_params* p, std::string& why) {
           " has a bit that is none of GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL";
     return GS_EINVAL;
   }
-  if (p->model == GS_MODEL_RUMOR && p->trials > 1) {
-    why = "GS_MODEL_RUMOR with trials > 1: the rumor model runs one trial per context (batched trials are not built)";
+  if (p->model == GS_MODEL_RUMOR && p->trials > 1 && !rumor_trials) {
+    why = "GS_MODEL_RUMOR with trials > 1: the rumor model runs one trial per context (gs_create_trials makes a batch)";
     return GS_EINVAL;
   }
   // batched trials (either model) live at trial << tlog | node in one 31-bit id space
@@ -252,7 +252,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
   c->win = !c->pp && !c->rumor && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
-  if (((c->trials > 1 && !c->ppt) || (shard && !c->pp)) && !c->win) {
+  if (((c->trials > 1 && !c->ppt && !c->rmt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
           "fanout/fanin <= 32, no GS_FLAG_TICK_ENGINE, at most 2^30 nodes per context or shard)";
     return GS_EINVAL;
@@ -271,9 +271,9 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const bool tick = !c->win && !c->pp && !c->rumor;
   // (batched push-pull trials build `next` in LDS: no second bitset, no summaries;
-  // the rumor model has the second bitset and no summaries)
+  // the rumor model has the second bitset and no summaries, its batched trials neither)
   const size_t b_sum = c->pp && !c->ppt ? al(pp_summary_total_words(s.W) * 8) : 0;
-  const size_t b_next = (c->pp && !c->ppt) || c->rumor ? al(s.W * 8) + b_sum : 0;
+  const size_t b_next = (c->pp && !c->ppt) || (c->rumor && !c->rmt) ? al(s.W * 8) + b_sum : 0;
   const size_t b_bits = al(s.W * 8), b_ring = tick ? al((size_t)s.R * s.W * 8) : 0,
                b_cflag = tick ? al((size_t)s.R * s.C * 4) : 0,
                b_clist = tick ? al((size_t)s.R * kShards * s.CS * 4) : 0,
@@ -332,6 +332,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
     pt.tlog = c->tlog;
     pt.kd = s.kd;
     pt.key = s.key;
+  }
+  if (c->rmt && !alloc_trial_rows(c, (size_t)c->trials * kMaxWindow * kTStatFields * 4, 0)) {
+    why = "cannot allocate the per-trial counters";
+    return GS_ENOMEM;
   }
   c->tacc.assign(c->trials, TrialAcc{});
   c->async_off = getenv("GS_SYNC_WINDOWS") != nullptr;
@@ -699,13 +703,20 @@ int ppt_masked_plan(const gs_ctx* c, PptPlan* plan, std::string& why) {
 // it, so gs_last_error(NULL) returns it.
 thread_local std::string g_create_err;
 
-int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out) {
+int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
+               bool rumor_trials) {
   std::string why;
   PptPlan pl;
-  int rc = check_params(params, why);
+  RmtPlan rpl;
+  int rc = check_params(params, rumor_trials, why);
   if (!rc) rc = check_ppt_n(params, device, why, &pl);
+  if (!rc) rc = check_rmt_n(params, device, why, &rpl);
   if (!rc) {
     gs_ctx* c = new gs_ctx();
+    if (rpl.block) {  // batched rumor trials: the plan check_rmt_n made for this device
+      c->rmt = true;
+      c->rplan = rpl;
+    }
     if (pl.block) {  // batched push-pull trials: the plan check_ppt_n made for this device
       c->ppt = true;
       c->pt.block = pl.block;

@@ -20,6 +20,7 @@
 #include "gs_comm.h"
 #include "gs_internal.h"
 #include "gs_ppt_plan.h"
+#include "gs_rmt_plan.h"
 
 namespace gs {
 
@@ -98,10 +99,14 @@ struct PpSparseBufs {
 
 // rumor mongering (gs_rumor.hip): the two hot lists [n] u32 (push modes) or the
 // hot, served and vain bitsets [W] (pull modes), the miss counts [n] u8, round
-// control (RumorCtl) and, once gs_read_removed asks, the removed bitset [W]:
+// control (RumorCtl) and, once gs_read_removed asks, the removed bitset [W].
+// A batched context (gs_rumor_trials.hip) has none of the lists: hot [W] and
+// miss [n] over the padded id space, and per-trial words (tri: the hot counts
+// [trials], then the started flags [trials]):
 // rumor_alloc / release_rumor
 struct RumorBufs {
-  Buf list[2], hot, served, vain, miss, ctlb, removed;
+  Buf list[2], hot, served, vain, miss, ctlb, removed, tri;
+  std::vector<uint32_t> hotn;  // batched: every trial's hot nodes after the last round run
   uint32_t cur = 0;   // list[cur] is the next round's read list
   uint32_t grid = 0;  // the round kernel's persistent grid (rumor_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
@@ -206,6 +211,9 @@ struct gs_ctx {
   // rumor mongering (gs_rumor.hip; d_next is its informed set being built)
   bool rumor = false;
   gs::RumorBufs rm;
+  // batched rumor trials (gs_create_trials; gs_rumor_trials.hip): a workgroup per trial
+  bool rmt = false;
+  gs::RmtPlan rplan{};
   // window engine (gs_win_*.hip)
   bool win = false;
   gs::WinState ws{};
@@ -322,7 +330,10 @@ constexpr uint32_t kSlots = 4;  // staging slots of the device-driven windows
 
 // gs_ctx.cpp
 extern thread_local std::string g_create_err;
-int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out);
+// rumor_trials: GS_MODEL_RUMOR with trials > 1 makes a batched rumor context
+// (gs_create_trials); every other create refuses the combination
+int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
+               bool rumor_trials = false);
 int create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out);
 int finish_rank(gs_ctx* c, gs_ctx** out);
 void destroy_one(gs_ctx* c);
@@ -396,5 +407,7 @@ int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
 int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
               int32_t* status);
 int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
+std::string rmt_limit_error(int device, uint32_t mode, uint64_t* lim);
+int check_rmt_n(const gs_params* p, int device, std::string& why, RmtPlan* pl);
 
 }  // namespace gs

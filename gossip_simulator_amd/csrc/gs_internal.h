@@ -230,7 +230,8 @@ constexpr uint32_t kStampPhases = 10;
 constexpr uint32_t kXStamp0 = 2 * kStampPhases;  // k_expand phases (GS_XSTAMPS builds) after k_resolve's
 constexpr uint32_t kDbgWords = kXStamp0 + 8;
 // per-trial window counters (batched trials)
-enum TStat : uint32_t { TS_FIRED = 0, TS_SENT = 1, TS_DEAD = 2, TS_RECV = 3, TS_CRASH = 4 };
+// (TS_HOT: batched rumor trials only -- the trial's hot nodes after the round)
+enum TStat : uint32_t { TS_FIRED = 0, TS_SENT = 1, TS_DEAD = 2, TS_RECV = 3, TS_CRASH = 4, TS_HOT = 5 };
 constexpr uint32_t kTStatFields = 8;
 
 // Key (node, counter word 3) of global id g for a draw of `kind`.
@@ -571,6 +572,39 @@ hipError_t rumor_pull_round(const DevState& s, const RumorState& r, uint32_t t, 
 hipError_t rumor_pull_commit(const DevState& s, const RumorState& r, uint32_t t, hipStream_t st);
 // out = recv & ~hot: the removed set.
 hipError_t rumor_pull_removed(const DevState& s, const RumorState& r, unsigned long long* out, hipStream_t st);
+
+// Batched rumor trials (gs_rumor_trials.hip): one
+// workgroup per trial, the trial's sets and miss bytes in LDS (plan:
+// gs_rmt_plan.h), up to kMaxWindow rounds per launch, every mode dense over
+// bitsets.  Nodes at trial << tlog | v as in every batched context.  Between
+// launches the hot set and the miss bytes live in global memory, in the
+// trial's own slot.
+struct RmtState {
+  const uint8_t* deg;
+  const uint32_t* ids;
+  unsigned long long* recv;         // [(trials << tlog) / 64] informed words
+  unsigned long long* hot;          // the same layout: the hot set between launches
+  uint8_t* miss;                    // [trials << tlog] miss counts between launches (unused with a coin)
+  const unsigned long long* crash;  // per-trial failure masks, laid out like recv (null: none)
+  uint32_t* tstat;                  // [trials][kMaxWindow][kTStatFields] per-round counters of every trial
+  uint32_t* nhot;                   // [trials] hot nodes of each trial after its last round (or the seed)
+  uint32_t n, trials, tlog, stride;
+  uint32_t block, lds_bytes;        // RmtPlan of (n, mode) on this device
+  uint32_t k, mode;                 // gs_params.rumor_k, rumor_mode
+  int32_t kd;
+  Key key;
+};
+// Per-workgroup LDS the device grants k_rmt_rounds of `mode` (bytes).  On an
+// error *where (may be null) names the HIP call that failed.
+hipError_t rmt_lds_limit(int device, uint32_t mode, uint64_t* limit, const char** where = nullptr);
+// Opt both instantiations of `mode` (masked and not) in to lds_bytes > 64 KiB of dynamic LDS on `device`.
+hipError_t rmt_prepare(int device, uint32_t mode, uint32_t lds_bytes);
+// Every trial's sender (`node`, or ~0u: the trial's keyed sender) informed
+// unless failed, and hot as the one-trial seeds make it; hot and miss zeroed
+// by the caller.  started[trial] = 1 if it was informed; s.nhot[trial] = 1 if hot.
+hipError_t rmt_seed(const RmtState& s, uint32_t node, uint32_t* started, hipStream_t st);
+// Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
+hipError_t rmt_rounds(const RmtState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
 
 // Launchers (gs_broadcast.hip).
 hipError_t launch_tick(const DevState& st, uint32_t tick, int mode, hipStream_t s);

@@ -1,6 +1,7 @@
 // gs_rumor_host.cpp -- the host side of rumor mongering (GS_MODEL_RUMOR,
 // DESIGN.md section 4.7): its buffers, the round loop and gs_run's stop rule.
-// One trial on one device; the kernels are in gs_rumor.hip.
+// One trial on one device (the kernels are in gs_rumor.hip), or a batch of
+// trials, a workgroup each (gs_create_trials; gs_rumor_trials.hip).
 #include "gs_ctx.h"
 
 namespace gs {
@@ -33,13 +34,217 @@ void rumor_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, bool p
   if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
 }
 
+// ---- batched trials --------------------------------
+
+RmtState rmt_state(const gs_ctx* c) {
+  RmtState r{};
+  r.deg = c->st.deg;
+  r.ids = c->st.ids;
+  r.recv = c->st.recv;
+  r.hot = (unsigned long long*)c->rm.hot.p;
+  r.miss = (uint8_t*)c->rm.miss.p;
+  r.crash = c->failed ? c->st.crash : nullptr;
+  r.tstat = c->bt.d_tstat;
+  r.nhot = (uint32_t*)c->rm.tri.p;
+  r.n = (uint32_t)c->p.n;
+  r.trials = c->trials;
+  r.tlog = c->tlog;
+  r.stride = c->st.stride;
+  r.block = c->rplan.block;
+  r.lds_bytes = (uint32_t)c->rplan.lds_bytes;
+  r.k = c->p.rumor_k;
+  r.mode = c->p.rumor_mode;
+  r.kd = c->st.kd;
+  r.key = c->st.key;
+  return r;
+}
+
+// Every trial's sender (k_rmt_seed): the trials that started are informed, and
+// the hot counts come back with them.
+int rmt_begin(gs_ctx* c, uint64_t sender) {
+  CK(c, hipSetDevice(c->dev));
+  const uint32_t T = c->trials;
+  const RmtState rs = rmt_state(c);
+  uint32_t* started = rs.nhot + T;
+  CK(c, hipMemsetAsync(c->rm.hot.p, 0, c->st.W * 8, c->stream));
+  CK(c, hipMemsetAsync(c->rm.miss.p, 0, c->st.n, c->stream));
+  CK(c, rmt_seed(rs, (uint32_t)sender, started, c->stream));
+  CK(c, hipMemcpyAsync(c->bt.h_tstat, rs.nhot, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  c->recv = c->pending = 0;
+  for (uint32_t tr = 0; tr < T; ++tr) {
+    c->rm.hotn[tr] = c->bt.h_tstat[tr];
+    c->tacc[tr].start = c->tacc[tr].recv = c->bt.h_tstat[T + tr];
+    c->recv += c->tacc[tr].recv;
+    c->pending += c->rm.hotn[tr];
+  }
+  c->begun = true;
+  return GS_OK;
+}
+
+// `ticks` rounds of every trial, at most kMaxWindow per launch (ppt_step's
+// loop); out[k] = the sum of the trials' rows, pending = their hot nodes.
+// tick_99 is taken at polls only (rumor_account's rule): every tick, or only
+// the call's last.
+int rmt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  CK(c, hipSetDevice(c->dev));
+  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
+  const RmtState rs = rmt_state(c);
+  const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
+  while (timing && c->ev.size() < 2) {
+    hipEvent_t ev;
+    CK(c, hipEventCreate(&ev));
+    c->ev.push_back(ev);
+  }
+  uint32_t done = 0;
+  while (done < ticks) {
+    const uint32_t batch = std::min<uint32_t>(ticks - done, kMaxWindow);
+    const uint64_t t0 = c->t + 1;
+    if (timing) CK(c, hipEventRecord(c->ev[0], c->stream));
+    CK(c, rmt_rounds(rs, (uint32_t)t0, batch, c->stream));
+    if (timing) CK(c, hipEventRecord(c->ev[1], c->stream));
+    CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, tb, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    if (timing) {
+      float ms = 0;
+      CK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+      c->timing.deliver_ms += ms;  // the rounds kernel: `batch` rounds of every trial
+      c->timing.deliver_launches++;
+    }
+    for (uint32_t k = 0; k < batch; ++k) {
+      const bool poll = every_tick_polls || done + k + 1 == ticks;
+      unsigned long long fired = 0, sent = 0, msgs = 0, hot = 0;
+      for (uint32_t tr = 0; tr < c->trials; ++tr) {
+        const uint32_t* r = c->bt.h_tstat + ((size_t)tr * kMaxWindow + k) * kTStatFields;
+        TrialAcc& a = c->tacc[tr];
+        a.fired += r[TS_FIRED];
+        a.sent += r[TS_SENT];
+        a.msgs += (uint64_t)r[TS_SENT] - r[TS_DEAD];
+        a.recv += r[TS_RECV];
+        if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = t0 + k;
+        c->rm.hotn[tr] = r[TS_HOT];
+        fired += r[TS_FIRED];
+        sent += r[TS_SENT];
+        msgs += (uint64_t)r[TS_SENT] - r[TS_DEAD];
+        c->recv += r[TS_RECV];
+        hot += r[TS_HOT];
+      }
+      c->t = t0 + k;
+      c->fired += fired;
+      c->sent += sent;
+      c->msgs += msgs;
+      c->pending = hot;
+      if (out) out[done + k] = gs_tick_stats{c->t, fired, sent, msgs, c->recv, 0, c->pending};
+    }
+    done += batch;
+  }
+  return GS_OK;
+}
+
+// rumor_run's rule per trial: a trial stops at the first poll at which it has
+// no hot node (covered or quiescent by the float32 rule at that poll), else at
+// max_ticks; the run ends when all have stopped.
+int rmt_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+            int32_t* status) {
+  size_t k = 0;
+  int32_t st = GS_RUN_MAX_TICKS;
+  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
+  for (;;) {
+    RC(rmt_step(c, poll, nullptr, false));
+    if (out && k < cap)
+      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
+    ++k;
+    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
+    uint32_t running = 0;
+    for (uint32_t tr = 0; tr < c->trials; ++tr) {
+      TrialAcc& a = c->tacc[tr];
+      if (a.status != GS_RUN_RUNNING) continue;
+      if (c->rm.hotn[tr] == 0) snap_trial(c, tr, covered(a.recv, c->p.n) ? GS_RUN_COVERED : GS_RUN_QUIESCENT);
+      else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);
+      else ++running;
+    }
+    if (trials_stopped(c, running, &st)) break;
+  }
+  if (nout) *nout = k;
+  if (status) *status = st;
+  return GS_OK;
+}
+
+// removed = recv & ~hot in every mode of the batch; trials x ceil(n/64) words, trial-major.
+int rmt_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
+  const uint64_t Wn = (c->p.n + 63) / 64;
+  if (!words || nwords < Wn * c->trials) return fail(c, GS_EINVAL, "need ceil(n/64) words per trial");
+  CK(c, hipSetDevice(c->dev));
+  if (!grow(c->rm.removed, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the removed set");
+  unsigned long long* d = (unsigned long long*)c->rm.removed.p;
+  RumorState r{};
+  r.hot = (unsigned long long*)c->rm.hot.p;
+  if (c->begun) CK(c, rumor_pull_removed(c->st, r, d, c->stream));
+  else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));  // (hot is the last run's: nothing is informed)
+  CK(c, hipMemcpy2DAsync(words, Wn * 8, d, ((size_t)1 << c->tlog) / 8, Wn * 8, c->trials, hipMemcpyDeviceToHost,
+                         c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
 }  // namespace
 
-// The combinations the model does not run yet (a batched or sharded version
-// is the follow-up): the creates with more than one device or process.
+// rmt_lds_limit with its failure in words ("" on success), as ppt_limit_error.
+std::string rmt_limit_error(int device, uint32_t mode, uint64_t* lim) {
+  const char* where = "";
+  const hipError_t e = rmt_lds_limit(device, mode, lim, &where);
+  if (e == hipSuccess) return std::string();
+  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
+         std::to_string((int)e) + ")";
+}
+
+// Batched rumor trials (gs_create_trials): n is bounded by what `device`
+// grants one workgroup (gs_rmt_plan.h), so it is validated with the other
+// parameters, after check_params and before any device state is set up; *pl
+// gets the plan (block 0: not such a context).  With no device to ask the
+// parameters were valid as far as they can be checked: GS_EDEVICE.
+int check_rmt_n(const gs_params* p, int device, std::string& why, RmtPlan* pl) {
+  *pl = RmtPlan{};
+  if (p->trials <= 1 || p->model != GS_MODEL_RUMOR) return GS_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    why = "no HIP device visible (libgossip_hip needs an MI355X)";
+    return GS_EDEVICE;
+  }
+  if (device < 0 || device >= ndev) {
+    why = "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)";
+    return GS_EDEVICE;
+  }
+  uint64_t lim = 0;
+  why = rmt_limit_error(device, p->rumor_mode, &lim);
+  if (!why.empty()) {
+    (void)hipGetLastError();
+    return GS_EDEVICE;
+  }
+  const RmtPlan plan = rmt_plan(p->n, p->rumor_mode, lim);
+  if (!plan.fits) {
+    why = "batched rumor trials keep a trial's sets and miss counts in one workgroup's LDS: with rumor_mode " +
+          std::to_string(p->rumor_mode) + " n must be <= " + std::to_string(rmt_max_n(p->rumor_mode, lim)) +
+          " on this device (gs_rumor_trials_max_n), not " + std::to_string(p->n);
+    return GS_EINVAL;
+  }
+  if (plan.lds_bytes > 65536 && rmt_prepare(device, p->rumor_mode, (uint32_t)plan.lds_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    why = "cannot raise the trial-resident rumor kernel's dynamic LDS limit";
+    return GS_EDEVICE;
+  }
+  *pl = plan;
+  return GS_OK;
+}
+
+// The combinations the model does not run: the creates with more than one
+// device or process (trials do not communicate: a caller puts one
+// gs_create_trials context per device, with an offset params.trial).
 int rumor_refuse(const gs_params* params, const char* what) {
   if (!params || params->model != GS_MODEL_RUMOR) return GS_OK;
-  g_create_err = std::string(what) + " with GS_MODEL_RUMOR: the rumor model runs one trial on one device (gs_create)";
+  g_create_err = std::string(what) + " with GS_MODEL_RUMOR: the rumor model runs on one device (gs_create, or "
+                 "gs_create_trials for a batch of trials)";
   fprintf(stderr, "%s: %s\n", what, g_create_err.c_str());
   return GS_EINVAL;
 }
@@ -48,8 +253,16 @@ int rumor_refuse(const gs_params* params, const char* what) {
 // lists, the miss bytes and the control block.  At n = 1e9: 4 + 4 + 1 GB,
 // from the block cache like every buffer of 64 MiB or more.  The pull modes
 // have three bitsets (3 x 125 MB) in place of the lists.
+// A batched context takes none of the lists: hot and miss over the padded id
+// space, and two words per trial.
 int rumor_alloc(gs_ctx* c) {
   const uint64_t n = c->st.n;
+  if (c->rmt) {
+    if (!grow(c->rm.hot, c->st.W * 8) || !grow(c->rm.miss, n) || !grow(c->rm.tri, (size_t)c->trials * 8))
+      return fail(c, GS_ENOMEM, "cannot allocate the batched rumor trials' hot sets and miss counts");
+    c->rm.hotn.assign(c->trials, 0);
+    return GS_OK;
+  }
   const bool sets = pull(c);
   if (sets ? !grow(c->rm.hot, c->st.W * 8) || !grow(c->rm.served, c->st.W * 8) || !grow(c->rm.vain, c->st.W * 8)
            : !grow(c->rm.list[0], n * 4) || !grow(c->rm.list[1], n * 4))
@@ -64,13 +277,14 @@ int rumor_alloc(gs_ctx* c) {
 // (removed grows at the first gs_read_removed)
 void release_rumor(gs_ctx* c) {
   RumorBufs& b = c->rm;
-  for (Buf* q : {&b.list[0], &b.list[1], &b.hot, &b.served, &b.vain, &b.miss, &b.ctlb, &b.removed}) release(*q);
+  for (Buf* q : {&b.list[0], &b.list[1], &b.hot, &b.served, &b.vain, &b.miss, &b.ctlb, &b.removed, &b.tri}) release(*q);
   if (b.h_ctl) (void)hipHostFree(b.h_ctl);
 }
 
 // The sender is informed unless failed (received = 1, as in push-pull) and
 // hot if it has a friend to call.
 int rumor_begin(gs_ctx* c, uint64_t sender) {
+  if (c->rmt) return rmt_begin(c, sender);
   CK(c, hipSetDevice(c->dev));
   // GS_RUMOR_GRID: the round kernel's blocks (read per broadcast, so tests can
   // make a short list take several passes of the grid)
@@ -99,6 +313,7 @@ int rumor_begin(gs_ctx* c, uint64_t sender) {
 // every_tick_polls: each tick is a poll (gs_step returns every tick's row);
 // else only the call's last tick is (gs_run).
 int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  if (c->rmt) return rmt_step(c, ticks, out, every_tick_polls);
   CK(c, hipSetDevice(c->dev));
   const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
   const RumorState rs = rumor_state(c);
@@ -159,6 +374,7 @@ int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
 int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
               int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
+  if (c->rmt) return rmt_run(c, poll, max_ticks, out, cap, nout, status);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
@@ -181,6 +397,7 @@ int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, 
 // (the pull modes: recv & ~hot).
 int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   if (!c->rumor) return fail(c, GS_EINVAL, "gs_read_removed needs a GS_MODEL_RUMOR context");
+  if (c->rmt) return rmt_read_removed(c, words, nwords);
   if (!words || nwords < c->st.W) return fail(c, GS_EINVAL, "need ceil(n/64) words");
   CK(c, hipSetDevice(c->dev));
   if (!grow(c->rm.removed, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the removed set");

@@ -36,13 +36,15 @@ class Config:
     timing: bool = False
     engine: str = "window"  # "window" (default) or "tick" (per-tick atomic engine)
     model: str = "flood"    # "flood" (the reference), "pushpull" (extension) or
-                            # "rumor" (extension, DESIGN.md 4.7: one trial, one device)
+                            # "rumor" (extension, DESIGN.md 4.7: one device; a batch of trials
+                            # through Simulator.batch)
     rumor_k: int = 2        # rumor: a node stops calling after this many calls that reached an
                             # informed peer (1..255)
     rumor_blind: bool = False  # rumor: an event every round a node is hot, reply or not (GS_RUMOR_BLIND)
     rumor_coin: bool = False   # rumor: an event removes with probability 1/rumor_k (GS_RUMOR_COIN)
     rumor_pull: bool = False   # rumor: every live node calls; hot nodes answer (GS_RUMOR_PULL)
-    trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3), either model
+    trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3): flood and
+                            # push-pull through Simulator(cfg), every model through Simulator.batch(cfg)
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
                               # rounds bottom-up once |I| >= 96n/256), "dense" (every round streams the
@@ -99,9 +101,11 @@ class Simulator:
     devices=None: one GPU (cfg.device), gs_create.  devices=[d0, d1, ...]:
     gs_create_multi -- a node-range-sharded broadcast over those devices
     (entries may repeat), or the trials split over them when cfg.trials > 1.
-    Simulator.rank(...): one rank of a multi-process run (gs_create_rank)."""
+    Simulator.rank(...): one rank of a multi-process run (gs_create_rank).
+    Simulator.batch(cfg): gs_create_trials -- as Simulator(cfg), and also a
+    batch of rumor trials (model="rumor", trials > 1), which gs_create refuses."""
 
-    def __init__(self, cfg: Config, devices=None, _rank=None):
+    def __init__(self, cfg: Config, devices=None, _rank=None, _batch=False):
         self.cfg = cfg
         self.L = _lib.load()
         self._p = cfg.to_params()
@@ -120,6 +124,9 @@ class Simulator:
             devs = (C.c_int * len(devices))(*[int(d) for d in devices])
             rc = self.L.gs_create_multi(C.byref(self._p), devs, len(devices), C.byref(h))
             what = "gs_create_multi"
+        elif _batch:
+            rc = self.L.gs_create_trials(C.byref(self._p), C.byref(h))
+            what = "gs_create_trials"
         else:
             rc = self.L.gs_create(C.byref(self._p), C.byref(h))
             what = "gs_create"
@@ -131,6 +138,15 @@ class Simulator:
         self.n = cfg.n
         self.trials = max(1, int(cfg.trials))
         self.words = (cfg.n + 63) // 64
+
+    @classmethod
+    def batch(cls, cfg: Config):
+        """cfg.trials trials at once on cfg.device through gs_create_trials: what
+        Simulator(cfg) makes, and for model="rumor" with trials > 1 a batched
+        rumor context (n <= rumor_trials_max_n of its mode).  Every call takes
+        the batched layouts: tables back to back, one mask per trial,
+        [trials, ceil(n/64)] sets."""
+        return cls(cfg, _batch=True)
 
     @classmethod
     def rank(cls, cfg: Config, nranks: int, rank: int, comm_id: bytes | None):
@@ -297,10 +313,11 @@ class Simulator:
         return w if self.trials == 1 else w.reshape(self.trials, self.words)
 
     def removed(self) -> np.ndarray:
-        """Rumor model: the removed nodes (informed, no longer calling), ceil(n/64) words."""
-        w = np.zeros(self.words, dtype=np.uint64)
+        """Rumor model: the removed nodes (informed, no longer calling), ceil(n/64)
+        words (a batch of trials: [trials, ceil(n/64)])."""
+        w = np.zeros(self.words * self.trials, dtype=np.uint64)
         self._check(self.L.gs_read_removed(self.h, w.ctypes.data, w.size), "gs_read_removed")
-        return w
+        return w if self.trials == 1 else w.reshape(self.trials, self.words)
 
     def trial_results(self) -> np.ndarray:
         """[trials, len(TRIAL_FIELDS)] int64: per trial its number, first
@@ -393,6 +410,23 @@ def pp_trials_max_n_masked(device: int = 0) -> int:
     if rc != 0:
         why = L.gs_last_error(None).decode(errors="replace")
         raise GossipError(rc, "gs_pp_trials_max_n_masked failed" + (f" ({why})" if why and why != "NULL context" else ""))
+    return int(out.value)
+
+
+def rumor_trials_max_n(mode=0, device: int = 0) -> int:
+    """Largest n a batched rumor context (Simulator.batch, model="rumor",
+    trials > 1) may have on `device` (gs_rumor_trials_max_n): the trial's sets
+    and miss counts live in one workgroup's LDS, so the limit depends on the
+    mode.  `mode`: the GS_RUMOR_* bits, or a Config (its rumor_blind,
+    rumor_coin and rumor_pull flags)."""
+    if isinstance(mode, Config):
+        mode = mode.to_params().rumor_mode
+    L = _lib.load()
+    out = C.c_uint64(0)
+    rc = L.gs_rumor_trials_max_n(int(device), int(mode), C.byref(out))
+    if rc != 0:
+        why = L.gs_last_error(None).decode(errors="replace")
+        raise GossipError(rc, "gs_rumor_trials_max_n failed" + (f" ({why})" if why and why != "NULL context" else ""))
     return int(out.value)
 
 

@@ -79,9 +79,13 @@ enum {
                               * no node is hot.  -droprate loses calls (no feedback either),
                               * -delaylow/-delayhigh/-crashrate are unused, gs_set_failed masks
                               * nodes (a failed callee gives no feedback).  gs_tick_stats.pending =
-                              * the hot nodes after the round.  One trial on one device: trials > 1,
-                              * gs_create_multi and gs_create_rank[_exchange] answer GS_EINVAL
-                              * (DESIGN.md section 4.7).  gs_params.rumor_mode (GS_RUMOR_*)
+                              * the hot nodes after the round.  One device: gs_create_multi and
+                              * gs_create_rank[_exchange] answer GS_EINVAL, and so does gs_create
+                              * with trials > 1; gs_create_trials makes a batch of trials (one
+                              * workgroup per trial, the trial's sets and miss counts in LDS, so
+                              * n <= gs_rumor_trials_max_n(); gs_set_failed takes one mask per
+                              * trial and needs no further LDS)
+                              * (DESIGN.md sections 4.7, 4.7.2).  gs_params.rumor_mode (GS_RUMOR_*)
                               * selects the other variants of Demers et al.; 0 is the model
                               * above */
 
@@ -116,7 +120,8 @@ typedef struct gs_params {
   /* Batched independent trials (config C3): trials trial .. trial+trials-1 of n
    * nodes each, run at once (one overlay, one broadcast per trial, keyed by
    * its trial number exactly as a one-trial context).  0 or 1 = one trial.
-   * Both models; trials << max(14, ceil(log2 n)) must be < 2^31.
+   * Every model (GS_MODEL_RUMOR: through gs_create_trials only);
+   * trials << max(14, ceil(log2 n)) must be < 2^31.
    * The reference runs one trial per process (simulator.go:207-253). */
   uint32_t trials;
   uint32_t rumor_k;    /* GS_MODEL_RUMOR: misses after which a node stops calling, 1..255
@@ -278,6 +283,40 @@ int gs_pp_trials_max_n(int device, uint64_t* n_max);
  * limit is about two thirds of gs_pp_trials_max_n's.  A context past it runs
  * unmasked; gs_set_failed refuses it with GS_EINVAL. */
 int gs_pp_trials_max_n_masked(int device, uint64_t* n_max);
+/* gs_create that also accepts GS_MODEL_RUMOR with params.trials > 1: a batched
+ * rumor context on params.device, trials params.trial .. params.trial +
+ * trials - 1 run at once, a workgroup each.  Every other parameter set is
+ * handled exactly as by gs_create (rumor with trials <= 1 included).
+ * Why there are two creates: gs_create has always answered GS_EINVAL for the
+ * rumor model with trials > 1, callers were told so and fall back to a loop of
+ * one-trial contexts when they see it, and programs test for that answer; it
+ * keeps giving it.  This create is the opt-in.  Every parameter check runs
+ * before any device call (rumor_k, rumor_mode, the 31-bit id space): bad
+ * parameters answer GS_EINVAL with the reason in gs_last_error(NULL) even
+ * where no device is visible, valid ones then answer GS_EDEVICE.  n past
+ * gs_rumor_trials_max_n() of the mode answers GS_EINVAL and names the limit.
+ * The batched context takes the usual calls with the batched layouts of the
+ * other models (gs_load_peers: tables back to back; gs_set_failed: one mask
+ * per trial; gs_broadcast_begin: a fixed node in every trial, or < 0 each
+ * trial's keyed sender; gs_step rows: sums over the trials, pending = their
+ * hot nodes; gs_read_received / _crashed / _removed: trials x ceil(n/64)
+ * words, trial-major).  Trial i behaves exactly like a one-trial gs_create
+ * context with params.trial + i, trial i's table and trial i's mask, round by
+ * round, also in rounds stepped after its own end.  gs_run: each trial stops
+ * at the first poll at which it has no hot node (GS_RUN_COVERED or
+ * GS_RUN_QUIESCENT by the float32 rule at that poll) or at max_ticks; the run
+ * ends when all have stopped, with the latest status among them.
+ * Trials do not communicate: to use several devices make one such context per
+ * device with an offset params.trial (gs_create_multi and gs_create_rank keep
+ * refusing the rumor model). */
+int gs_create_trials(const gs_params* params, gs_ctx** out);
+/* Largest n a batched rumor context of gs_params.rumor_mode `rumor_mode` may
+ * have on `device`: three bitsets (five with GS_RUMOR_PULL and feedback) and,
+ * unless GS_RUMOR_COIN, a miss byte per node must fit the LDS the device
+ * grants one workgroup.  gs_create_trials refuses a larger n with GS_EINVAL.
+ * A failure mask does not lower it.  GS_EINVAL for a bad mode bit, GS_EDEVICE
+ * where the device cannot be asked. */
+int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max);
 
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
@@ -348,7 +387,8 @@ int gs_read_crashed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 /* GS_MODEL_RUMOR: the removed nodes -- informed and no longer hot (rumor_k
  * events or a lost coin toss, or in the push modes no friend to call; with
  * GS_RUMOR_PULL an informed live node with no friend is hot, not removed) --
- * in the same layout, words[ceil(n/64)].
+ * in the same layout, words[ceil(n/64)] (a gs_create_trials batch: trials x
+ * ceil(n/64) words, trial-major; removed = informed and not hot in every mode).
  * GS_EINVAL on a context of another model. */
 int gs_read_removed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 
