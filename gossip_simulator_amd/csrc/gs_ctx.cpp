@@ -114,7 +114,7 @@ int alloc_window(gs_ctx* c) {
                b_fhist = al(((size_t)w.ncoarse * 256 + 1) * 8), b_fbase = al(((size_t)w.nfine + 1) * 8),
                b_ffill = al((size_t)w.nfine * 8),
                b_sst = al((size_t)kStatShards * kMaxWindow * kStatFields * 8),
-               b_rlcnt = al((size_t)w.nfine * 4),
+               b_rlcnt = al((size_t)w.nfine * 4) + al(((size_t)w.nfine + 2) * 4),
                b_tsum = al((size_t)w.ncoarse * kMaxWindow * 8) + al(((size_t)w.ncoarse + 1) * 8);
   const size_t total = b_fc + 2 * b_units + b_small + b_fhist + b_fbase + b_ffill + b_sst + b_rlcnt + b_tsum;
   if (dev_malloc(&c->wn.d_win, total) != hipSuccess)
@@ -136,7 +136,8 @@ int alloc_window(gs_ctx* c) {
   w.fstart = (unsigned long long*)q; q += b_fbase;
   w.ffill = (unsigned long long*)q; q += b_ffill;
   w.sstats = (unsigned long long*)q; q += b_sst;
-  w.rlcnt = (uint32_t*)q; q += b_rlcnt;
+  w.rlcnt = (uint32_t*)q; q += al((size_t)w.nfine * 4);
+  w.lgl = (uint32_t*)q; q += al(((size_t)w.nfine + 2) * 4);
   w.tsum = (unsigned long long*)q; q += al((size_t)w.ncoarse * kMaxWindow * 8);
   w.toff = (unsigned long long*)q; q += al(((size_t)w.ncoarse + 1) * 8);
   if (dev_malloc(&c->wn.d_rlmsg, (size_t)w.nfine * kRolledCap * 4) != hipSuccess)

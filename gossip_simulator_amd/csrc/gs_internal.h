@@ -145,6 +145,8 @@ struct WinState {
   uint32_t* rollw;               // [2W] nodes with a crash-roll receipt in the window (k_part2 -> k_resolve)
   uint32_t* rlmsg;               // [nfine][kRolledCap] receipts at rolled nodes (k_resolve -> k_resolve_rolled)
   uint32_t* rlcnt;               // [nfine] their counts (zeroed by the consumer)
+  uint32_t* lgl;                 // [2 + nfine] buckets whose rolled list overflowed: count, workgroups
+                                 // done, buckets (k_resolve -> k_resolve_large, which zeroes the two)
   unsigned long long* stats;
   uint32_t* err;
   uint32_t* fcount;              // [R][nfine] fire-list lengths

@@ -64,12 +64,13 @@ struct ResolveLds {
   uint32_t cls;
   unsigned long long stamp[2][kStampPhases];  // GS_STAMPS: [M >= 1024][phase] cycles (thread 0)
   unsigned long long tlast;
-};  // ~72 KB: two workgroups per CU
+};  // 78 KB: two workgroups per CU
 static_assert(kBitTicks <= kMaxWindow, "window ticks fit the message format");
 static_assert(sizeof(uint32_t) * kFineNodes <= sizeof(((ResolveLds*)0)->cnt), "the infection list fits");
 
 // GS_STAMPS diagnostics: thread 0 adds the cycles since the last stamp to phase i.
-__device__ __forceinline__ void stamp(const WinState& w, ResolveLds& sm, uint32_t i) {
+template <class Lds>
+__device__ __forceinline__ void stamp(const WinState& w, Lds& sm, uint32_t i) {
   if (w.dbg && threadIdx.x == 0) {
     const unsigned long long t = __builtin_amdgcn_s_memtime();
     if (i) sm.stamp[sm.cls][i] += t - sm.tlast;
@@ -155,7 +156,8 @@ __device__ __forceinline__ void resolve_tick(const WinState& w, ResolveLds& sm, 
 // zeroed.  Block-uniform call.
 // acc_ni[k / 2] holds tick k's count in bits 16 * (k & 1) (<= 32 per bucket,
 // <= 256 buckets per lane).
-__device__ __forceinline__ void flush_counts(const WinState& w, ResolveLds& sm, uint32_t (&acc_ni)[kBitTicks / 2],
+template <class Lds>
+__device__ __forceinline__ void flush_counts(const WinState& w, Lds& sm, uint32_t (&acc_ni)[kBitTicks / 2],
                                              uint32_t L, uint32_t trial) {
 #pragma unroll
   for (uint32_t k = 0; k < kBitTicks; ++k) {
@@ -458,12 +460,334 @@ __device__ __forceinline__ void resolve_body(const WinState& w, uint32_t t0, uin
   if (w.dbg && tid < 2 * kStampPhases) atomicAdd(&w.dbg[tid], (&sm.stamp[0][0])[tid]);
   if (!w.tstat) flush_counts(w, sm, acc_ni, L, ~0u);
 }
-__global__ __launch_bounds__(kResolveBlock, GS_RESOLVE_WAVES) void k_resolve(const WinState w, uint32_t t0, uint32_t L) {
+__global__ __launch_bounds__(kResolveBlock, GS_RESOLVE_WAVES) void k_resolve2(const WinState w, uint32_t t0, uint32_t L) {
   resolve_body(w, t0, L);
 }
-__global__ __launch_bounds__(kResolveBlock, GS_RESOLVE_WAVES) void k_resolve_m(const WinState* __restrict__ ws,
-                                                                                uint32_t L) {
+__global__ __launch_bounds__(kResolveBlock, GS_RESOLVE_WAVES) void k_resolve2_m(const WinState* __restrict__ ws,
+                                                                                 uint32_t L) {
   resolve_body(ws[blockIdx.y], 0u, L);
+}
+
+// k_resolve: the bit path alone on a budget that lets three workgroups share a
+// CU (six waves per SIMD to hide the dependent LDS round trips behind): at
+// most 80 VGPRs and 53 KB of LDS.  Against resolve_body:
+//   * a bucket whose rolled list overflows is appended to w.lgl and skipped
+//     (k_resolve_large resolves it after this kernel), so the 64-KB counter
+//     arm is gone;
+//   * the infection list holds kInfCap entries in place of cr0 (dead after the
+//     receipts), filled and drained in rounds when a bucket informs more;
+//   * four loads in flight per lane (six waves x 4 per SIMD against four x 8);
+//     the per-tick infection words are recomputed from b1 when they are
+//     listed; the uncounted receipts are 6-bit fields of one register pair.
+constexpr uint32_t kInfCap = 6656;  // C5's densest buckets inform ~5,700 nodes in a window: one round
+constexpr uint32_t kResolveWaves3 = 6;  // min waves per SIMD: three 512-thread workgroups per CU
+struct ResolveLds3 {
+  uint32_t b1[kBitTicks][kBitWords];
+  union {
+    uint2 cr0[kBitWords];     // receipts phase (see ResolveLds)
+    uint32_t inf[kInfCap];    // after it: infected nodes, loc | tick << 14
+  };
+  uint32_t fc[kWinMaxRing];
+  uint32_t st[kMaxWindow][4];
+  uint32_t dead[kMaxWindow];
+  uint32_t blist[kResolveMaxBuckets];
+  unsigned long long bstart[kResolveMaxBuckets];
+  uint32_t bcnt[kResolveMaxBuckets];
+  uint32_t ndup;
+  uint32_t ninf;
+  uint32_t err;
+  uint32_t nb;
+  uint32_t cls;
+  unsigned long long stamp[2][kStampPhases];
+  unsigned long long tlast;
+};
+static_assert(sizeof(ResolveLds3) <= 53 * 1024, "three workgroups per CU");
+static_assert(kBitTicks * 6 <= 64, "6-bit dead counts per tick in one register pair");
+
+__device__ __forceinline__ void resolve3_body(const WinState& w, uint32_t t0, uint32_t L) {
+  __shared__ ResolveLds3 sm;
+  const uint32_t tid = threadIdx.x, G = gridDim.x;
+  L = win_live(w, t0, L);
+  if (!L) return;
+  if (tid < kMaxWindow * 4) (&sm.st[0][0])[tid] = 0;
+  if (tid == 0) { sm.nb = 0; sm.cls = 0; }
+  if (tid < 2 * kStampPhases) (&sm.stamp[0][0])[tid] = 0;
+  __syncthreads();
+  {
+    const uint32_t f = blockIdx.x + tid * G;
+    const unsigned long long fl = tid < kResolveMaxBuckets && f < w.nfine ? w.ffill[f] : 0ull;
+    const bool ne = fl > kSmallMax;  // small: k_resolve_small
+    const uint32_t at = wave_append(&sm.nb, ne);
+    if (ne) {
+      sm.blist[at] = f;
+      sm.bstart[at] = w.fstart[f];
+      sm.bcnt[at] = (uint32_t)fl;
+    }
+  }
+  __syncthreads();
+  const uint32_t nb = sm.nb;
+  stamp(w, sm, 0);
+  uint32_t* rwg = (uint32_t*)w.recv;
+  uint32_t* cwg = (uint32_t*)w.crash;
+  uint32_t acc_ni[kBitTicks / 2];  // this lane's infections per tick over all its buckets
+#pragma unroll
+  for (uint32_t k = 0; k < kBitTicks / 2; ++k) acc_ni[k] = 0;
+  constexpr uint32_t kU = 4;  // loads in flight per lane
+  constexpr uint32_t kBatch = kResolveBlock * kU;
+  // messages p0 + u * kResolveBlock + tid of a bucket (gm, M >= 1): the index
+  // clamped to M - 1, so a lane past the end holds a copy of the last receipt
+  auto ld = [&](const uint32_t* gm, uint32_t M, uint32_t p0, uint32_t (&m)[kU]) {
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) {
+      const uint32_t p = p0 + u * kResolveBlock + tid;
+      m[u] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(gm) + ((p < M ? p : M - 1) << 2));
+    }
+  };
+  // the next bucket's state words and first batch of messages are loaded
+  // while this bucket finishes (branch-free, masked where they are used: see
+  // resolve_body).  Without the batch, the windows of a few thousand receipts
+  // per bucket pay a load latency per bucket: slower than resolve_body.
+  uint32_t pm[kU], p_recv0 = 0, p_crash0 = 0, p_roll0 = 0, p_fcv = 0;
+  bool p_in = false;
+  auto prefetch = [&](uint32_t j) {
+    const uint32_t f = sm.blist[j];
+    const uint64_t wi = ((uint64_t)(f << kFineLog) >> 5) + tid;
+    const bool in = wi < w.W * 2;
+    const uint64_t wc = in ? wi : w.W * 2 - 1;
+    p_in = in;
+    p_recv0 = rwg[wc];
+    p_crash0 = cwg[wc];
+    p_roll0 = w.rollw[wc];
+    p_fcv = w.fcount[(size_t)(tid < w.R ? tid : 0u) * w.nfine + f];
+    ld(w.fmsg + sm.bstart[j], sm.bcnt[j], 0, pm);
+  };
+  if (nb > 0) prefetch(0);
+  for (uint32_t i = 0; i < nb; ++i) {
+    const uint32_t f = sm.blist[i], M = sm.bcnt[i];
+    const uint32_t* gm = w.fmsg + sm.bstart[i];
+    uint32_t m[kU];
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) m[u] = pm[u];
+    const uint32_t node0 = f << kFineLog;
+    const uint64_t wi = ((uint64_t)node0 >> 5) + tid;
+    const bool in = p_in;
+    const uint32_t recv0 = in ? p_recv0 : 0u, crash0 = in ? p_crash0 : 0u, roll0 = in ? p_roll0 : 0u;
+    if (roll0) w.rollw[wi] = 0u;  // consumed: the next window starts clear
+    const uint32_t rollw = roll0 & ~crash0;
+#pragma unroll
+    for (uint32_t k = 0; k < kBitTicks; ++k)
+      if (k < L) sm.b1[k][tid] = 0;
+    sm.cr0[tid] = make_uint2(crash0, rollw);
+    if (tid < w.R) sm.fc[tid] = p_fcv;
+    if (tid < kMaxWindow) sm.dead[tid] = 0;
+    if (tid == 0) { sm.ndup = 0; sm.ninf = 0; sm.err = M >= (1u << 28) ? 3 : 0; sm.cls = M >= 1024 ? 1 : 0; }
+    __syncthreads();
+    stamp(w, sm, 1);
+    // receipts: as resolve_body's, the uncounted ones in 6-bit fields per tick
+    // (a lane adds <= kU per batch: flushed every 15 batches)
+    unsigned long long dd = 0;
+    auto flush_dead = [&]() {
+      while (dd) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(dd) / 6;
+        atomicAdd(&sm.dead[b], (uint32_t)(dd >> (6 * b)) & 63u);
+        dd &= ~(63ull << (6 * b));
+      }
+    };
+    for (uint32_t p0 = 0, nbat = 0; p0 < (sm.err == 3 ? 0u : M); p0 += kBatch, ++nbat) {
+      uint32_t mn[kU];
+      if (p0 + kBatch < M) ld(gm, M, p0 + kBatch, mn);
+      uint2 sp[kU];
+#pragma unroll
+      for (uint32_t u = 0; u < kU; ++u) {
+        // (a lane past the end sets its copy's bit again: no change)
+        const uint32_t loc = msg_loc(m[u]);
+        atomicOr(&sm.b1[msg_tick(m[u])][loc >> 5], 1u << (loc & 31));  // no return
+        sp[u] = GS_RESOLVE_CR0(loc);
+      }
+      uint32_t dm = 0;  // bit u: receipt u is at a rolled node
+#pragma unroll
+      for (uint32_t u = 0; u < kU; ++u) {
+        const uint32_t sh = msg_loc(m[u]) & 31, k = msg_tick(m[u]);
+        const uint32_t valid = p0 + u * kResolveBlock + tid < M ? 1u : 0u;
+        // crashed before the window: not counted (:108)
+        dd += (unsigned long long)((sp[u].x >> sh) & valid) << (6 * k);
+        dm |= ((sp[u].y >> sh) & valid) << u;
+      }
+      if (nbat % 15 == 14) flush_dead();
+      if (__ballot(dm != 0)) {
+        const uint32_t nd = __popc(dm);
+        uint32_t pre = 0, tot = 0;  // wave prefix of nd (<= 4)
+#pragma unroll
+        for (uint32_t bb = 0; bb < 3; ++bb) {
+          const unsigned long long bal = __ballot((nd >> bb) & 1u);
+          pre += lanes_below(bal) << bb;
+          tot += (uint32_t)__popcll(bal) << bb;
+        }
+        uint32_t base = 0;
+        if (lane_id() == 0) base = atomicAdd(&sm.ndup, tot);
+        uint32_t at = __builtin_amdgcn_readfirstlane(base) + pre;
+#pragma unroll
+        for (uint32_t u = 0; u < kU; ++u) if ((dm >> u) & 1u) {
+          if (at < kRolledCap) w.rlmsg[(size_t)f * kRolledCap + at] = m[u] & ((1u << 19) - 1);
+          else sm.err = 3;
+          ++at;
+        }
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kU; ++u) m[u] = mn[u];
+    }
+    flush_dead();
+    stamp(w, sm, 2);
+    __syncthreads();
+    if (i + 1 < nb) prefetch(i + 1);
+    const bool large = sm.err == 3;  // its rolled list overflowed: k_resolve_large's
+    if (tid == 0) {
+      // the rolled list goes to k_resolve_rolled (none of a large bucket)
+      w.rlcnt[f] = large ? 0u : sm.ndup;
+      if (large) w.lgl[2 + atomicAdd(&w.lgl[0], 1u)] = f;
+    }
+    stamp(w, sm, 3);
+    if (!large) {
+      if (tid < L && sm.dead[tid]) atomicAdd(&sm.st[tid][0], sm.dead[tid]);
+      // plain nodes: informed at their first receipt, tick by tick
+      const uint32_t plain = ~(crash0 | rollw);
+      uint32_t rw = recv0, ninf = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kBitTicks; ++k) {
+        if (k >= L) continue;
+        const uint32_t infS = sm.b1[k][tid] & plain & ~rw;  // :117-121
+        rw |= infS;
+        const uint32_t ni = __popc(infS);
+        acc_ni[k / 2] += ni << (16 * (k & 1));
+        ninf += ni;
+      }
+      stamp(w, sm, 4);
+      stamp(w, sm, 5);
+      stamp(w, sm, 6);
+      if (in && rw != recv0) rwg[wi] = rw;
+      // this lane's place in the bucket's infection list
+      uint32_t at0;
+      {
+        uint32_t pre = 0, tot = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 9; ++b) {  // ninf <= 32 * kBitTicks < 512
+          const unsigned long long bal = __ballot((ninf >> b) & 1u);
+          pre += lanes_below(bal) << b;
+          tot += (uint32_t)__popcll(bal) << b;
+        }
+        uint32_t base = 0;
+        if (tot && lane_id() == 0) base = atomicAdd(&sm.ninf, tot);
+        at0 = __builtin_amdgcn_readfirstlane(base) + pre;
+      }
+      // rounds of kInfCap: entries [r0, r0 + kInfCap) are listed (loc | tick
+      // << 14, over cr0: the receipts are done), then Broadcast() by the whole
+      // block.  Every consumer of the fire lists is order-free.
+      for (uint32_t r0 = 0;; r0 += kInfCap) {
+        uint32_t at = at0 - r0, r = recv0;
+#pragma unroll
+        for (uint32_t k = 0; k < kBitTicks; ++k) {
+          if (k >= L) continue;
+          uint32_t x = sm.b1[k][tid] & plain & ~r;
+          r |= x;
+          for (; x; x &= x - 1, ++at)
+            if (at < kInfCap) sm.inf[at] = (tid * 32 + __builtin_ctz(x)) | (k << kFineLog);
+        }
+        __syncthreads();
+        stamp(w, sm, 7);
+        const uint32_t left = sm.ninf - r0;
+        for (uint32_t q = tid; q < min(left, kInfCap); q += kResolveBlock) {
+          // Broadcast() of an infected node x = loc | tick << 14 (:122,
+          // :141-142): fire at t + off
+          const uint32_t x = sm.inf[q];
+          const uint32_t loc = msg_loc(x), t = t0 + msg_tick(x);
+          uint32_t knode0, c3order;  // the bucket's Philox keys (a bucket lies inside one trial)
+          node_key(w.tlog, w.tmask, w.key, (uint64_t)w.base + node0, K_ORDER, knode0, c3order);
+          const uint32_t c3delay = (c3order & 0xFFFFFFu) | (K_DELAY << 24);
+          const uint32_t off = fire_offset(w.delay_low, w.delay_span,
+                                           philox(knode0 + loc, t, 0, c3delay, w.key.k0, w.key.k1).x);
+          const uint32_t slot = (t + off) % w.R;
+          const uint32_t pos = atomicAdd(&sm.fc[slot], 1u);
+          w.flist[((size_t)slot * w.nfine + f) * kFineNodes + pos] = (uint16_t)loc;
+        }
+        if (left <= kInfCap) break;
+        __syncthreads();  // drained before the next round lists
+      }
+    }
+    __syncthreads();
+    stamp(w, sm, 8);
+    if (!large && tid < w.R) w.fcount[(size_t)tid * w.nfine + f] = sm.fc[tid];
+    stamp(w, sm, 9);
+    if (w.dbg && tid == 0) sm.stamp[sm.cls][0] += 1;
+    // batched trials: the bucket's counters go to its trial's rows
+    if (w.tstat) flush_counts(w, sm, acc_ni, L, (uint32_t)(((uint64_t)w.base + node0) >> w.tlog));
+  }
+  if (w.dbg && tid < 2 * kStampPhases) atomicAdd(&w.dbg[tid], (&sm.stamp[0][0])[tid]);
+  if (!w.tstat) flush_counts(w, sm, acc_ni, L, ~0u);
+}
+__global__ __launch_bounds__(kResolveBlock, kResolveWaves3) void k_resolve(const WinState w, uint32_t t0, uint32_t L) {
+  resolve3_body(w, t0, L);
+}
+__global__ __launch_bounds__(kResolveBlock, kResolveWaves3) void k_resolve_m(const WinState* __restrict__ ws,
+                                                                             uint32_t L) {
+  resolve3_body(ws[blockIdx.y], 0u, L);
+}
+
+// The buckets k_resolve listed in w.lgl (count, workgroups done, buckets):
+// their rolled lists overflowed, so every node is replayed per tick from
+// per-node counters (resolve_tick).  One workgroup per bucket; the last
+// workgroup to finish clears the list for the next window.  No flood of the
+// paper's configurations lists a bucket: the launch leaves at once.
+__device__ __forceinline__ void resolve_large_body(const WinState& w, uint32_t t0, uint32_t L) {
+  __shared__ ResolveLds sm;
+  const uint32_t n = w.lgl[0];
+  if (!n) return;
+  const uint32_t tid = threadIdx.x;
+  L = win_live(w, t0, L);
+  if (L) {
+    if (tid < kMaxWindow * 4) (&sm.st[0][0])[tid] = 0;
+    uint32_t acc_ni[kBitTicks / 2];  // (the bit path's: none here)
+#pragma unroll
+    for (uint32_t k = 0; k < kBitTicks / 2; ++k) acc_ni[k] = 0;
+    uint32_t* rwg = (uint32_t*)w.recv;
+    uint32_t* cwg = (uint32_t*)w.crash;
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+      const uint32_t f = w.lgl[2 + j], M = (uint32_t)w.ffill[f];
+      const uint32_t* gm = w.fmsg + w.fstart[f];
+      const uint32_t node0 = f << kFineLog;
+      const uint64_t wi = ((uint64_t)node0 >> 5) + tid;
+      const bool in = wi < w.W * 2;
+      const uint32_t recv0 = in ? rwg[wi] : 0u, crash0 = in ? cwg[wi] : 0u;
+      uint4* c4 = reinterpret_cast<uint4*>(sm.cnt);
+      for (uint32_t q = tid; q < kFineNodes / 4; q += kResolveBlock) c4[q] = make_uint4(0, 0, 0, 0);
+      sm.recv[tid] = recv0;
+      sm.crash[tid] = crash0;
+      if (tid < w.R) sm.fc[tid] = w.fcount[(size_t)tid * w.nfine + f];
+      if (tid == 0) sm.err = 0;
+      __syncthreads();
+      for (uint32_t k = 0; k < L; ++k) resolve_tick(w, sm, f, gm, 0, M, k, t0 + k);
+      const uint32_t rw = sm.recv[tid], cw = sm.crash[tid];
+      if (in) {
+        if (rw != recv0) rwg[wi] = rw;
+        if (cw != crash0) cwg[wi] = cw;
+      }
+      if (tid < w.R) w.fcount[(size_t)tid * w.nfine + f] = sm.fc[tid];
+      if (tid == 0 && sm.err == 1) atomicOr(w.err, kErrArrivals);
+      if (w.tstat) flush_counts(w, sm, acc_ni, L, (uint32_t)(((uint64_t)w.base + node0) >> w.tlog));
+      else __syncthreads();
+    }
+    if (!w.tstat) flush_counts(w, sm, acc_ni, L, ~0u);
+  }
+  __syncthreads();
+  if (tid == 0 && atomicAdd(&w.lgl[1], 1u) == gridDim.x - 1) {
+    w.lgl[0] = 0;
+    w.lgl[1] = 0;
+  }
+}
+__global__ __launch_bounds__(kResolveBlock) void k_resolve_large(const WinState w, uint32_t t0, uint32_t L) {
+  resolve_large_body(w, t0, L);
+}
+__global__ __launch_bounds__(kResolveBlock) void k_resolve_large_m(const WinState* __restrict__ ws, uint32_t L) {
+  resolve_large_body(ws[blockIdx.y], 0u, L);
 }
 
 // Small buckets (1..kSmallMax receipts in the window): one wave per bucket.
@@ -692,16 +1016,33 @@ __global__ __launch_bounds__(ROLLED ? kRolledBlock : kSmallBlock) void k_resolve
 
 }  // namespace
 
+// A/B switch GS_RESOLVE_OCC3=0: the two-per-CU k_resolve2 with its own large
+// path; read once per process.
+static bool resolve_occ3() {
+  static const bool on = [] { const char* e = getenv("GS_RESOLVE_OCC3"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
 hipError_t win_resolve(const WinState& w, uint32_t t0, uint32_t L, hipStream_t s) {
-  // persistent: two workgroups per CU (the LDS holds two), each owning <= 256 buckets
+  // persistent, each workgroup owning <= 256 buckets.  k_resolve: three
+  // resident per CU, six queued (the second three even out the first three's
+  // tails: 55.4 against 55.9 ms per C5 step; four, not a multiple of three,
+  // 57.1).  k_resolve2: two, all resident.
   const uint32_t cus = device_cus();
-  static const uint32_t per_cu = [] { const char* e = getenv("GS_RESOLVE_PER_CU"); return e ? (uint32_t)std::max(atoi(e), 1) : 2u; }();  // A/B knob
+  const bool occ3 = resolve_occ3();
+  static const uint32_t per_cu_env = [] { const char* e = getenv("GS_RESOLVE_PER_CU"); return e ? (uint32_t)std::max(atoi(e), 1) : 0u; }();  // A/B knob
+  const uint32_t per_cu = per_cu_env ? per_cu_env : occ3 ? 6u : 2u;
   uint32_t G = std::min<uint32_t>(w.nfine, per_cu * cus);
   G = std::max<uint32_t>(G, (w.nfine + kResolveMaxBuckets - 1) / kResolveMaxBuckets);
   const uint32_t gs = (w.nfine + kSmallBlock / 64 - 1) / (kSmallBlock / 64);
   hipLaunchKernelGGL(k_resolve_small<false>, dim3(gs), dim3(kSmallBlock), 0, s, w, t0, L);
   static_assert(kSmallMax == 64 * 4, "the two bodies cover 1..kSmallMax");
-  hipLaunchKernelGGL(k_resolve, dim3(G), dim3(kResolveBlock), 0, s, w, t0, L);
+  if (occ3) {
+    hipLaunchKernelGGL(k_resolve, dim3(G), dim3(kResolveBlock), 0, s, w, t0, L);
+    hipLaunchKernelGGL(k_resolve_large, dim3(std::min<uint32_t>(w.nfine, cus)), dim3(kResolveBlock), 0, s, w, t0, L);
+  } else {
+    hipLaunchKernelGGL(k_resolve2, dim3(G), dim3(kResolveBlock), 0, s, w, t0, L);
+  }
   // k_resolve_rolled: small blocks (the E = 16 key arrays take 4 KB per wave; blocks finish independently)
   hipLaunchKernelGGL(k_resolve_small<true>, dim3((w.nfine + kRolledBlock / 64 - 1) / (kRolledBlock / 64)),
                      dim3(kRolledBlock), 0, s, w, t0, L);
@@ -710,13 +1051,20 @@ hipError_t win_resolve(const WinState& w, uint32_t t0, uint32_t L, hipStream_t s
 
 hipError_t win_resolve_g(const WinGroup& g, uint32_t L, hipStream_t s) {
   const uint32_t cus = device_cus();
-  // k_resolve's two workgroups per CU split over the shards (each still owns
-  // <= kResolveMaxBuckets buckets of its shard)
-  uint32_t G = std::min<uint32_t>(g.nfine_max, (2 * cus + g.M - 1) / g.M);
+  // k_resolve's resident workgroups per CU split over the shards (each still
+  // owns <= kResolveMaxBuckets buckets of its shard)
+  const bool occ3 = resolve_occ3();
+  uint32_t G = std::min<uint32_t>(g.nfine_max, ((occ3 ? 3 : 2) * cus + g.M - 1) / g.M);
   G = std::max<uint32_t>(G, (g.nfine_max + kResolveMaxBuckets - 1) / kResolveMaxBuckets);
   const uint32_t gs = (g.nfine_max + kSmallBlock / 64 - 1) / (kSmallBlock / 64);
   hipLaunchKernelGGL(k_resolve_small_m<false>, dim3(gs, g.M), dim3(kSmallBlock), 0, s, g.wr, L);
-  hipLaunchKernelGGL(k_resolve_m, dim3(G, g.M), dim3(kResolveBlock), 0, s, g.wr, L);
+  if (occ3) {
+    hipLaunchKernelGGL(k_resolve_m, dim3(G, g.M), dim3(kResolveBlock), 0, s, g.wr, L);
+    hipLaunchKernelGGL(k_resolve_large_m, dim3(std::min<uint32_t>(g.nfine_max, (cus + g.M - 1) / g.M), g.M),
+                       dim3(kResolveBlock), 0, s, g.wr, L);
+  } else {
+    hipLaunchKernelGGL(k_resolve2_m, dim3(G, g.M), dim3(kResolveBlock), 0, s, g.wr, L);
+  }
   hipLaunchKernelGGL(k_resolve_small_m<true>, dim3((g.nfine_max + kRolledBlock / 64 - 1) / (kRolledBlock / 64), g.M),
                      dim3(kRolledBlock), 0, s, g.wr, L);
   return hipGetLastError();

@@ -17,15 +17,19 @@ def s(n):
         return "probe"
     if m.group(1) == "k_resolve_rolled" or (m.group(1) == "k_resolve_small" and m.group(2) == "<true>"):
         return "rolled"  # the rolled-node replay after k_resolve, same window
+    if m.group(1) == "k_resolve_large":
+        return "large"  # the overflowed buckets' per-tick replay after k_resolve, same window
+    if m.group(1) == "k_resolve2":
+        return "k_resolve"  # GS_RESOLVE_OCC3=0: the two-per-CU kernel
     return m.group(1)
 
 
 seq = [(s(n), (e - b) / 1e3) for n, b, e in rows
-       if s(n) in ("k_expand", "k_part2", "k_resolve_small", "k_resolve", "probe", "rolled")]
+       if s(n) in ("k_expand", "k_part2", "k_resolve_small", "k_resolve", "probe", "rolled", "large")]
 wins, cur = [], {}
 for name, us in seq:
-    if name == "rolled" and wins:
-        wins[-1]["rolled"] = wins[-1].get("rolled", 0) + us
+    if name in ("rolled", "large") and wins:
+        wins[-1][name] = wins[-1].get(name, 0) + us
         continue
     cur[name] = cur.get(name, 0) + us
     if name == "k_resolve":
@@ -36,6 +40,7 @@ tot = {}
 for i, w in enumerate(wins[-nwin:]):
     extra = f"  probe {w['probe']:8.1f}" if "probe" in w else ""
     extra += f"  rolled {w['rolled']:6.1f}" if "rolled" in w else ""
+    extra += f"  large {w['large']:5.1f}" if "large" in w else ""
     print(f"{i:3d} expand {w.get('k_expand', 0):8.1f}  part2 {w.get('k_part2', 0):8.1f}  "
           f"resolve {w.get('k_resolve', 0):8.1f}  small {w.get('k_resolve_small', 0):6.1f}{extra}")
     for k, v in w.items():
