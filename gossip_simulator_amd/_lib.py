@@ -23,7 +23,7 @@ GS_FLAG_PP_EARLY = 16
 GS_FLAG_PP_TOPDOWN = 32
 GS_FLAG_PP_BOTTOM = 64
 GS_FLAG_PP_ANSWER = 128
-GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR = 0, 1, 2
+GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR, GS_MODEL_MEDIAN = 0, 1, 2, 3
 GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL = 1, 2, 4
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
 GS_COMM_ID_BYTES = 128
@@ -39,7 +39,7 @@ EXPORTS = (
     "gs_create_rank", "gs_shard_info", "gs_trial_results", "gs_set_trial",
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
     "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
-    "gs_create_trials", "gs_rumor_trials_max_n",
+    "gs_create_trials", "gs_rumor_trials_max_n", "gs_read_median_state",
 )
 
 
@@ -62,9 +62,11 @@ class Params(C.Structure):
         ("trial", C.c_uint32),
         ("device", C.c_int32),
         ("flags", C.c_uint32),
-        ("model", C.c_uint32),  # GS_MODEL_FLOOD = 0 (reference), GS_MODEL_PUSHPULL = 1, GS_MODEL_RUMOR = 2
+        ("model", C.c_uint32),  # GS_MODEL_FLOOD = 0 (reference), GS_MODEL_PUSHPULL = 1, GS_MODEL_RUMOR = 2,
+        # GS_MODEL_MEDIAN = 3
         ("trials", C.c_uint32),  # batched independent trials (config C3); 0/1 = one
-        ("rumor_k", C.c_uint32),  # GS_MODEL_RUMOR: misses after which a node stops calling (1..255)
+        ("rumor_k", C.c_uint32),  # GS_MODEL_RUMOR: misses after which a node stops calling (1..255);
+        # GS_MODEL_MEDIAN: counter steps and final-phase rounds (1..127)
         ("rumor_mode", C.c_uint32),  # GS_MODEL_RUMOR: GS_RUMOR_* bits (0 = push, feedback, counter)
         ("reserved32_", C.c_uint32),
         ("reserved_", C.c_uint64 * 4),
@@ -146,6 +148,7 @@ def load():
         "gs_read_received": ([ctx, vp, sz], C.c_int),
         "gs_read_crashed": ([ctx, vp, sz], C.c_int),
         "gs_read_removed": ([ctx, vp, sz], C.c_int),
+        "gs_read_median_state": ([ctx, vp, sz], C.c_int),
         "gs_timing_get": ([ctx, P(Timing)], C.c_int),
         "gs_shard_timing": ([ctx, C.c_uint32, P(Timing)], C.c_int),
         "gs_format_float32": ([C.c_float, C.c_char_p, sz], sz),

@@ -6,7 +6,8 @@
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
 // (-seed -trial -trials -device -peers -maxticks -model -k) are not echoed in
 // the parameter block, so stdout keeps the reference's shape.  -model rumor
-// runs to its own end and adds the residue and the messages per node.  -trials T > 1 runs
+// and -model median run to their own end and add the residue and the messages
+// per node (-model median: one trial only).  -trials T > 1 runs
 // T independent trials in one batched context and prints one line per trial;
 // with -model rumor (gs_create_trials) the trial lines carry the model's own
 // figures and a summary line their mean and sample standard deviation, and
@@ -33,6 +34,7 @@ struct Flag {
   std::string defv;  // Go default as printed
   bool echo;         // part of the reference's flag set (echoed, :197-204)
   std::string val;
+  bool given = false;  // set on the command line
 };
 
 std::vector<Flag> g_flags;
@@ -111,6 +113,7 @@ void parse(int argc, char** argv) {
       if (name == "h" || name == "help") { usage(); exit(0); }
       die_usage("flag provided but not defined: -" + name);
     }
+    f->given = true;
     if (!has && !strcmp(f->type, "bool")) {  // -name alone sets a bool; -name=false clears it
       value = "true";
       has = true;
@@ -206,9 +209,11 @@ int main(int argc, char** argv) {
       {"gpus", "int", "node-range shards over devices device .. device+gpus-1 (one process)", "1", false,
        "1"},
       {"peers", "string", "injected peer-table file (skips overlay construction)", "", false, ""},
-      {"model", "string", "dissemination model: flood (the reference), pushpull or rumor (extensions)",
+      {"model", "string", "dissemination model: flood (the reference), pushpull, rumor or median (extensions)",
        "flood", false, "flood"},
-      {"k", "int", "rumor model: a node stops calling after this many calls that reached an informed peer",
+      {"k", "int", "rumor model: a node stops calling after this many calls that reached an informed peer; "
+       "median model: the counter steps and the rounds of the final phase, 1..127 (default there: "
+       "ceil(log2 log2 n) + 1)",
        "2", false, "2"},
       {"blind", "bool", "rumor model: a hot node loses interest without waiting for a reply (GS_RUMOR_BLIND)",
        "false", false, "false"},
@@ -222,13 +227,31 @@ int main(int argc, char** argv) {
   parse(argc, argv);
   // every flag is checked before the parameter echo and before any device call
   const std::string model = find("model")->val;
-  if (model != "flood" && model != "pushpull" && model != "rumor") {
-    fprintf(stderr, "invalid value \"%s\" for flag -model: want flood, pushpull or rumor\n", model.c_str());
+  if (model != "flood" && model != "pushpull" && model != "rumor" && model != "median") {
+    fprintf(stderr, "invalid value \"%s\" for flag -model: want flood, pushpull or rumor, or median\n",
+            model.c_str());
     return 2;
   }
-  const long long rumor_k = ival("k");
+  long long rumor_k = ival("k");
+  if (model == "median" && !find("k")->given) {
+    // The counter must outlast the spread, or B nodes whose partners are all done stay B (DESIGN.md
+    // section 4.8): O(ln ln n) steps in the paper; ceil(log2 log2 n) + 1 here.
+    const double l2 = std::log2(std::max<double>(4.0, (double)ival("n")));
+    rumor_k = std::min<long long>(127, (long long)std::ceil(std::log2(l2)) + 1);
+  }
   if (model == "rumor" && (rumor_k < 1 || rumor_k > 255)) {
     fprintf(stderr, "invalid value \"%s\" for flag -k: want 1..255\n", find("k")->val.c_str());
+    usage();
+    return 2;
+  }
+  if (model == "median" && (rumor_k < 1 || rumor_k > 127)) {
+    fprintf(stderr, "invalid value \"%s\" for flag -k: -model median wants 1..127\n", find("k")->val.c_str());
+    usage();
+    return 2;
+  }
+  if (model == "median" && ival("trials") > 1) {
+    fprintf(stderr, "flag -trials %s with -model median: the median-counter model runs one trial on one device "
+            "(GS_MODEL_MEDIAN)\n", find("trials")->val.c_str());
     usage();
     return 2;
   }
@@ -268,7 +291,12 @@ int main(int argc, char** argv) {
   p.seed = strtoull(find("seed")->val.c_str(), nullptr, 10);
   p.trial = (uint32_t)strtoull(find("trial")->val.c_str(), nullptr, 10);
   p.device = (int32_t)ival("device");
-  p.model = model == "pushpull" ? GS_MODEL_PUSHPULL : model == "rumor" ? GS_MODEL_RUMOR : GS_MODEL_FLOOD;
+  p.model = model == "pushpull" ? GS_MODEL_PUSHPULL
+            : model == "rumor"  ? GS_MODEL_RUMOR
+            : model == "median" ? GS_MODEL_MEDIAN
+                                : GS_MODEL_FLOOD;
+  if (p.model == GS_MODEL_MEDIAN) p.rumor_k = (uint32_t)rumor_k;
+  const bool self_ending = p.model == GS_MODEL_RUMOR || p.model == GS_MODEL_MEDIAN;  // runs to its own end
   if (p.model == GS_MODEL_RUMOR) {
     p.rumor_k = (uint32_t)rumor_k;
     p.rumor_mode = rumor_mode;
@@ -406,7 +434,7 @@ int main(int argc, char** argv) {
   gs_tick_stats tot{};
   gs_totals(c, &tot);
   const double bc_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
-  if (p.model == GS_MODEL_RUMOR) {  // the model's own outputs, at quiescence
+  if (self_ending) {  // the model's own outputs, at quiescence
     char rb[64], mb[64];
     gs_format_float32(1.0f - (float)tot.received / (float)p.n, rb, sizeof(rb));
     gs_format_float32((float)tot.messages / (float)p.n, mb, sizeof(mb));
@@ -427,7 +455,7 @@ int main(int argc, char** argv) {
     return 3;
   }
   uint64_t t99 = tot.tick;
-  if (p.model == GS_MODEL_RUMOR) {  // the run went on to quiescence: the first covered poll
+  if (self_ending) {  // the run went on to quiescence: the first covered poll
     gs_trial_stats tr{};
     size_t ntr = 0;
     if (gs_trial_results(c, &tr, 1, &ntr) == GS_OK && ntr == 1 && tr.tick_99) t99 = tr.tick_99;

@@ -189,6 +189,7 @@ int gs_create_trials(const gs_params* params, gs_ctx** out) {
   g_create_err.clear();
   if (!out) return GS_EINVAL;
   *out = nullptr;
+  RC(median_refuse(params, "gs_create_trials"));
   return create_one(params, params ? params->device : 0, false, 1, 0, out, true);
 }
 
@@ -248,6 +249,7 @@ int gs_create_rank(const gs_params* params, int device, int nranks, int rank, co
   if (!out || !params || nranks < 1 || rank < 0 || rank >= nranks) return GS_EINVAL;
   *out = nullptr;
   RC(rumor_refuse(params, "gs_create_rank"));
+  RC(median_refuse(params, "gs_create_rank"));
   const uint32_t T = std::max<uint32_t>(1, params->trials);
   if (T > 1) {  // this rank's share of the trials, no communication
     gs_params mp = *params;
@@ -289,6 +291,7 @@ int gs_create_rank_exchange(const gs_params* params, int device, int nranks, int
       rank >= nranks)
     return GS_EINVAL;
   RC(rumor_refuse(params, "gs_create_rank_exchange"));
+  RC(median_refuse(params, "gs_create_rank_exchange"));
   if (params->model == GS_MODEL_FLOOD && std::max<uint32_t>(1, params->trials) == 1 && !ex->all_to_allv) {
     fprintf(stderr, "gs_create_rank_exchange: flood shards need the all_to_allv callback\n");
     return GS_EINVAL;
@@ -489,6 +492,7 @@ int gs_broadcast_begin(gs_ctx* c, int64_t sender) {
     return GS_OK;
   }
   if (c->rumor) return rumor_begin(c, s);
+  if (c->median) return median_begin(c, s);
   if (c->pp && (c->group || c->pp_shard)) return pp_shard_begin(c, s);
   if (c->pp) {  // push-pull: the sender is informed (unless failed)
     CK(c, hipSetDevice(c->dev));
@@ -575,6 +579,7 @@ int gs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out) {
     return GS_OK;
   }
   if (c->rumor) return rumor_step(c, ticks, out, true);
+  if (c->median) return median_step(c, ticks, out, true);
   if (c->pp && (c->group || c->pp_shard)) return pp_shard_step(c, ticks, out);
   if (c->group) return shard_step(c, c->gr.mem, ticks, out);
   if (c->shard) return abort_rank(c, shard_step(c, {c}, ticks, out));
@@ -605,6 +610,7 @@ int gs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, siz
     return GS_OK;
   }
   if (c->rumor) return rumor_run(c, poll, max_ticks, out, cap, nout, status);
+  if (c->median) return median_run(c, poll, max_ticks, out, cap, nout, status);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   const bool trials = c->trials > 1 && !c->group;
@@ -740,7 +746,13 @@ int gs_read_crashed(gs_ctx* c, uint64_t* words, size_t nwords) {
 
 int gs_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   if (!c) return GS_EINVAL;
+  if (c->median) return median_read_removed(c, words, nwords);
   return rumor_read_removed(c, words, nwords);
+}
+
+int gs_read_median_state(gs_ctx* c, uint8_t* st, size_t n) {
+  if (!c) return GS_EINVAL;
+  return median_read_state(c, st, n);
 }
 
 int gs_timing_get(gs_ctx* c, gs_timing* out) {

@@ -28,8 +28,16 @@ int check_params(const gs_params* p, bool rumor_trials, std::string& why) {
     return GS_EINVAL;
   }
   if (ring_slots(*p) > 4096) { why = "delayhigh must be <= 4096"; return GS_EINVAL; }
-  if (p->model > GS_MODEL_RUMOR) {
-    why = "model must be GS_MODEL_FLOOD, GS_MODEL_PUSHPULL or GS_MODEL_RUMOR";
+  if (p->model > GS_MODEL_MEDIAN) {
+    why = "model must be GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR or GS_MODEL_MEDIAN";
+    return GS_EINVAL;
+  }
+  if (p->model == GS_MODEL_MEDIAN && (p->rumor_k < 1 || p->rumor_k > 127)) {
+    why = "GS_MODEL_MEDIAN needs 1 <= rumor_k <= 127, not " + std::to_string(p->rumor_k);
+    return GS_EINVAL;
+  }
+  if (p->model == GS_MODEL_MEDIAN && p->trials > 1) {
+    why = "GS_MODEL_MEDIAN with trials > 1: the median-counter model runs one trial per context";
     return GS_EINVAL;
   }
   if (p->model == GS_MODEL_RUMOR && (p->rumor_k < 1 || p->rumor_k > 255)) {
@@ -202,6 +210,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   const uint32_t stride0 = (uint32_t)std::max(c->p.fanout, c->p.fanin);
   c->pp = c->p.model == GS_MODEL_PUSHPULL;
   c->rumor = c->p.model == GS_MODEL_RUMOR;
+  c->median = c->p.model == GS_MODEL_MEDIAN;
   c->pp_l2_only = (c->p.flags & GS_FLAG_PP_L2_ONLY) != 0;
   c->trials = std::max<uint32_t>(1, c->p.trials);
   c->ntot = c->p.n;
@@ -214,6 +223,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   c->rank = rank;
   if (shard && c->rumor) {
     why = "GS_MODEL_RUMOR runs on one device: no node-range shards";
+    return GS_EINVAL;
+  }
+  if (shard && c->median) {
+    why = "GS_MODEL_MEDIAN runs on one device: no node-range shards";
     return GS_EINVAL;
   }
   if (shard) {
@@ -251,7 +264,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // Engine: the window engine unless the ring is too long for LDS, rows are
   // wider than 32 or the tick engine is forced; push-pull has its own kernels.
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
-  c->win = !c->pp && !c->rumor && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
+  c->win = !c->pp && !c->rumor && !c->median && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
   if (((c->trials > 1 && !c->ppt && !c->rmt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
@@ -270,7 +283,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // One state allocation, 256-B aligned sub-buffers; everything before
   // `stats` is per-broadcast state that gs_reset clears.
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const bool tick = !c->win && !c->pp && !c->rumor;
+  const bool tick = !c->win && !c->pp && !c->rumor && !c->median;
   // (batched push-pull trials build `next` in LDS: no second bitset, no summaries;
   // the rumor model has the second bitset and no summaries, its batched trials neither)
   const size_t b_sum = c->pp && !c->ppt ? al(pp_summary_total_words(s.W) * 8) : 0;
@@ -316,6 +329,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   }
   if (c->rumor) {
     int rc = rumor_alloc(c);
+    if (rc) { why = c->err; return rc; }
+  }
+  if (c->median) {
+    int rc = median_alloc(c);
     if (rc) { why = c->err; return rc; }
   }
   if (c->ppt) {  // per-trial counter rows and the stall check's buffers
@@ -528,6 +545,7 @@ int finish_rank(gs_ctx* c, gs_ctx** out) {
 // over `devices`.
 int create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out) {
   RC(rumor_refuse(params, "gs_create_multi"));
+  RC(median_refuse(params, "gs_create_multi"));
   gs_ctx* g = new gs_ctx();
   g->group = true;
   g->p = *params;
@@ -756,6 +774,7 @@ void destroy_one(gs_ctx* c) {
   release_trials(c);
   release_sparse(c);
   release_rumor(c);
+  release_median(c);
   release_async(c);
   release_dd(c);
   if (c->own) (void)hipStreamDestroy(c->own);

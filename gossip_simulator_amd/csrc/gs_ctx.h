@@ -2,7 +2,8 @@
 // the error macros and the few host functions that cross the engine files
 // (gs_ctx.cpp lifetime, gs_peers.cpp tables, gs_windows.cpp / gs_shards.cpp
 // the flood engines, gs_pushpull_host.cpp push-pull, gs_rumor_host.cpp rumor
-// mongering, gs_api.cpp the entry points).
+// mongering, gs_median_host.cpp median-counter push-pull, gs_api.cpp the entry
+// points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include "gossip.h"
 #include "gs_comm.h"
 #include "gs_internal.h"
+#include "gs_median.h"
 #include "gs_ppt_plan.h"
 #include "gs_rmt_plan.h"
 
@@ -109,6 +111,16 @@ struct RumorBufs {
   std::vector<uint32_t> hotn;  // batched: every trial's hot nodes after the last round run
   uint32_t cur = 0;   // list[cur] is the next round's read list
   uint32_t grid = 0;  // the round kernel's persistent grid (rumor_begin)
+  RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
+};
+
+// median-counter push-pull (gs_median.hip): the state bytes [n], the
+// own-contribution bytes [n], the tally [n] u64, the gotb / gotc bitsets [W],
+// round control (a RumorCtl) and, once gs_read_removed asks, the done bitset
+// [W]: median_alloc / release_median
+struct MedianBufs {
+  Buf st, own, tally, gotb, gotc, ctlb, done;
+  uint32_t grid = 0;  // the round kernel's persistent grid (median_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
 };
 
@@ -214,6 +226,9 @@ struct gs_ctx {
   // batched rumor trials (gs_create_trials; gs_rumor_trials.hip): a workgroup per trial
   bool rmt = false;
   gs::RmtPlan rplan{};
+  // median-counter push-pull (gs_median.hip)
+  bool median = false;
+  gs::MedianBufs md;
   // window engine (gs_win_*.hip)
   bool win = false;
   gs::WinState ws{};
@@ -409,5 +424,16 @@ int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, 
 int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
 std::string rmt_limit_error(int device, uint32_t mode, uint64_t* lim);
 int check_rmt_n(const gs_params* p, int device, std::string& why, RmtPlan* pl);
+
+// gs_median_host.cpp
+int median_refuse(const gs_params* params, const char* what);
+int median_alloc(gs_ctx* c);
+void release_median(gs_ctx* c);
+int median_begin(gs_ctx* c, uint64_t sender);
+int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls);
+int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+               int32_t* status);
+int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
+int median_read_state(gs_ctx* c, uint8_t* st, size_t n);
 
 }  // namespace gs

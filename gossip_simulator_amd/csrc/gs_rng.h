@@ -17,6 +17,7 @@
 //                                   order, first_crash() below
 //   kind RUMOR (extension)           ctr {v, t, 0, .}            out[0] -> U_deg, out[1] -> U_100
 //                                   ctr {v, t, 1, .}            out[0] -> U_k: the coin of v's event
+//   kind MEDIAN (extension)          ctr {v, t, 0, .}            out[0] -> U_deg, out[1] -> U_100
 // with counter word 3 = kind << 24 | trial.  U_m(r) = floor(r*m / 2^32).
 #pragma once
 #include <stdint.h>
@@ -30,6 +31,7 @@ enum Kind : uint32_t {
   K_PUSHPULL = 9,  // push-pull extension: peer pick + loss per (node, round)
   K_ORDER = 10,    // receipt order of a (node, tick): first-crash position
   K_RUMOR = 11     // rumor mongering: peer pick + loss per (hot node, round)
+  , K_MEDIAN = 12  // median-counter push-pull: peer pick + loss per (calling node, round)
 };
 
 struct u32x4 { uint32_t x, y, z, w; };

@@ -35,11 +35,13 @@ class Config:
     device: int = 0
     timing: bool = False
     engine: str = "window"  # "window" (default) or "tick" (per-tick atomic engine)
-    model: str = "flood"    # "flood" (the reference), "pushpull" (extension) or
+    model: str = "flood"    # "flood" (the reference), "pushpull" (extension),
                             # "rumor" (extension, DESIGN.md 4.7: one device; a batch of trials
-                            # through Simulator.batch)
+                            # through Simulator.batch) or "median" (extension, DESIGN.md 4.8:
+                            # median-counter push-pull, one trial on one device)
     rumor_k: int = 2        # rumor: a node stops calling after this many calls that reached an
-                            # informed peer (1..255)
+                            # informed peer (1..255); median: the counter steps and the rounds of
+                            # the final phase (1..127)
     rumor_blind: bool = False  # rumor: an event every round a node is hot, reply or not (GS_RUMOR_BLIND)
     rumor_coin: bool = False   # rumor: an event removes with probability 1/rumor_k (GS_RUMOR_COIN)
     rumor_pull: bool = False   # rumor: every live node calls; hot nodes answer (GS_RUMOR_PULL)
@@ -54,7 +56,8 @@ class Config:
                               # pull-answer)
 
     PP_ROUNDS = ("auto", "dense", "early", "topdown", "bottom", "answer")
-    MODELS = {"flood": _lib.GS_MODEL_FLOOD, "pushpull": _lib.GS_MODEL_PUSHPULL, "rumor": _lib.GS_MODEL_RUMOR}
+    MODELS = {"flood": _lib.GS_MODEL_FLOOD, "pushpull": _lib.GS_MODEL_PUSHPULL, "rumor": _lib.GS_MODEL_RUMOR,
+              "median": _lib.GS_MODEL_MEDIAN}
 
     def flags(self, timing: bool | None = None) -> int:
         if self.pp_rounds not in self.PP_ROUNDS:
@@ -76,7 +79,7 @@ class Config:
         p.drop_rate, p.crash_rate = self.droprate, self.crashrate
         p.seed, p.trial, p.device = self.seed, self.trial, self.device
         if self.model not in self.MODELS:
-            raise ValueError(f"model must be 'flood', 'pushpull' or 'rumor', not {self.model!r}")
+            raise ValueError(f"model must be 'flood', 'pushpull', 'rumor' or 'median', not {self.model!r}")
         p.model = self.MODELS[self.model]
         if self.model == "rumor":
             if not 1 <= int(self.rumor_k) <= 255:
@@ -85,6 +88,10 @@ class Config:
             p.rumor_mode = (_lib.GS_RUMOR_BLIND if self.rumor_blind else 0) | \
                 (_lib.GS_RUMOR_COIN if self.rumor_coin else 0) | \
                 (_lib.GS_RUMOR_PULL if self.rumor_pull else 0)
+        if self.model == "median":
+            if not 1 <= int(self.rumor_k) <= 127:
+                raise ValueError(f"rumor_k must be in 1..127 for model 'median', not {self.rumor_k!r}")
+            p.rumor_k = int(self.rumor_k)
         p.flags = self.flags()
         p.trials = max(1, int(self.trials))
         return p
@@ -314,10 +321,19 @@ class Simulator:
 
     def removed(self) -> np.ndarray:
         """Rumor model: the removed nodes (informed, no longer calling), ceil(n/64)
-        words (a batch of trials: [trials, ceil(n/64)])."""
+        words (a batch of trials: [trials, ceil(n/64)]).  Median model: the done
+        nodes (state D)."""
         w = np.zeros(self.words * self.trials, dtype=np.uint64)
         self._check(self.L.gs_read_removed(self.h, w.ctypes.data, w.size), "gs_read_removed")
         return w if self.trials == 1 else w.reshape(self.trials, self.words)
+
+    def median_state(self) -> np.ndarray:
+        """Median model: every node's state byte, [n] uint8: 0 = uninformed, m in
+        1..rumor_k = informed with counter m, rumor_k + c = round c of the final
+        phase, 255 = done (gs_read_median_state)."""
+        st = np.zeros(self.n, dtype=np.uint8)
+        self._check(self.L.gs_read_median_state(self.h, st.ctypes.data, st.size), "gs_read_median_state")
+        return st
 
     def trial_results(self) -> np.ndarray:
         """[trials, len(TRIAL_FIELDS)] int64: per trial its number, first

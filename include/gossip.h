@@ -88,6 +88,28 @@ enum {
                               * (DESIGN.md sections 4.7, 4.7.2).  gs_params.rumor_mode (GS_RUMOR_*)
                               * selects the other variants of Demers et al.; 0 is the model
                               * above */
+#define GS_MODEL_MEDIAN 3u   /* extension, no reference counterpart: the median-counter push-pull of
+                              * Karp, Schindelhauer, Shenker and Voecking, a push-pull that ends by
+                              * itself.  One synchronous round per tick; every live node with a
+                              * friend that is not done calls one Philox-picked friend, and a kept
+                              * call to a live friend is a connection on which the rumor moves both
+                              * ways (messages counts the active ends).  A node is uninformed (A),
+                              * informed with a counter 1..rumor_k (B), in the final phase of
+                              * rumor_k rounds (C) or done (D); a B node advances its counter when
+                              * more of the round's partners are B with a counter at least its own
+                              * than are A or B with a smaller one, a C partner moves an A or B
+                              * node straight to C, and after the counter's rumor_k steps and the
+                              * rumor_k rounds of C the node is done and silent.  The run ends by
+                              * itself when no node is B or C.  rumor_k must be 1..127; -droprate
+                              * loses calls, -delaylow/-delayhigh/-crashrate and rumor_mode are
+                              * unused, gs_set_failed masks nodes (no connection reaches them).
+                              * gs_tick_stats.pending = the B and C nodes after the round.  An
+                              * informed node that nobody connects to, or whose partners are all
+                              * done already, stays B, so such a run ends GS_RUN_MAX_TICKS (a
+                              * short counter strands some nodes this way: DESIGN.md section 4.8).
+                              * One trial on one device: trials > 1,
+                              * gs_create_trials, gs_create_multi and gs_create_rank[_exchange]
+                              * answer GS_EINVAL */
 
 /* Variants of GS_MODEL_RUMOR (gs_params.rumor_mode, any combination; the other
  * models ignore the field; another bit answers GS_EINVAL). */
@@ -124,7 +146,8 @@ typedef struct gs_params {
    * trials << max(14, ceil(log2 n)) must be < 2^31.
    * The reference runs one trial per process (simulator.go:207-253). */
   uint32_t trials;
-  uint32_t rumor_k;    /* GS_MODEL_RUMOR: misses after which a node stops calling, 1..255
+  uint32_t rumor_k;    /* GS_MODEL_RUMOR: misses after which a node stops calling, 1..255;
+                        * GS_MODEL_MEDIAN: the counter steps and the final phase's rounds, 1..127
                         * (the other models ignore it) */
   uint32_t rumor_mode; /* GS_MODEL_RUMOR: GS_RUMOR_* bits, 0 = push with feedback and counter
                         * (the other models ignore it) */
@@ -389,8 +412,15 @@ int gs_read_crashed(gs_ctx* ctx, uint64_t* words, size_t nwords);
  * GS_RUMOR_PULL an informed live node with no friend is hot, not removed) --
  * in the same layout, words[ceil(n/64)] (a gs_create_trials batch: trials x
  * ceil(n/64) words, trial-major; removed = informed and not hot in every mode).
+ * GS_MODEL_MEDIAN: the done nodes (state D).
  * GS_EINVAL on a context of another model. */
 int gs_read_removed(gs_ctx* ctx, uint64_t* words, size_t nwords);
+/* GS_MODEL_MEDIAN: every node's state byte, st[n]: 0 = uninformed (A), m in
+ * 1..rumor_k = informed with counter m (B-m), rumor_k + c = round c of the final
+ * phase (C-c, c in 1..rumor_k), 255 = done (D).  gs_read_received gives the
+ * nodes whose byte is not 0, gs_read_removed those at 255.  GS_EINVAL on a
+ * context of another model. */
+int gs_read_median_state(gs_ctx* ctx, uint8_t* st, size_t n);
 
 int gs_timing_get(gs_ctx* ctx, gs_timing* out);
 /* The same for shard `index` of a sharded (or batched) context's members;
