@@ -31,9 +31,9 @@ Layers:
 """
 from ._lib import (GS_RUN_COVERED, GS_RUN_MAX_TICKS, GS_RUN_QUIESCENT,  # noqa: F401
                    GossipError, load)
-from .engine import (Config, Simulator, covered, memory_stats, pp_trials_max_n,  # noqa: F401
-                     pp_trials_max_n_masked, rumor_trials_max_n, trim)
+from .engine import (Config, Simulator, covered, median_trials_max_n, memory_stats,  # noqa: F401
+                     pp_trials_max_n, pp_trials_max_n_masked, rumor_trials_max_n, trim)
 
 __all__ = ["Config", "Simulator", "GossipError", "covered", "load", "trim", "memory_stats", "pp_trials_max_n",
-           "pp_trials_max_n_masked", "rumor_trials_max_n", "GS_RUN_COVERED",
+           "pp_trials_max_n_masked", "rumor_trials_max_n", "median_trials_max_n", "GS_RUN_COVERED",
            "GS_RUN_QUIESCENT", "GS_RUN_MAX_TICKS"]

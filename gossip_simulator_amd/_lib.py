@@ -40,6 +40,7 @@ EXPORTS = (
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
     "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
     "gs_create_trials", "gs_rumor_trials_max_n", "gs_read_median_state",
+    "gs_create_batch", "gs_median_trials_max_n",
 )
 
 
@@ -134,6 +135,7 @@ def load():
         "gs_strerror": ([C.c_int], C.c_char_p),
         "gs_create": ([P(Params), P(vp)], C.c_int),
         "gs_create_trials": ([P(Params), P(vp)], C.c_int),
+        "gs_create_batch": ([P(Params), P(vp)], C.c_int),
         "gs_destroy": ([ctx], None),
         "gs_last_error": ([ctx], C.c_char_p),
         "gs_load_peers": ([ctx, vp, vp, C.c_uint32], C.c_int),
@@ -171,6 +173,7 @@ def load():
         "gs_pp_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_pp_trials_max_n_masked": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_rumor_trials_max_n": ([C.c_int, C.c_uint32, P(C.c_uint64)], C.c_int),
+        "gs_median_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -4,10 +4,12 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -trials -device -peers -maxticks -model -k) are not echoed in
+// (-seed -trial -trials -device -peers -maxticks -model -k -batch) are not echoed in
 // the parameter block, so stdout keeps the reference's shape.  -model rumor
 // and -model median run to their own end and add the residue and the messages
-// per node (-model median: one trial only).  -trials T > 1 runs
+// per node (-model median: one trial, or -batch T trials through
+// gs_create_batch, printed like the rumor model's with a stranded column: the
+// nodes still active at the trial's stop).  -trials T > 1 runs
 // T independent trials in one batched context and prints one line per trial;
 // with -model rumor (gs_create_trials) the trial lines carry the model's own
 // figures and a summary line their mean and sample standard deviation, and
@@ -215,6 +217,8 @@ int main(int argc, char** argv) {
        "median model: the counter steps and the rounds of the final phase, 1..127 (default there: "
        "ceil(log2 log2 n) + 1)",
        "2", false, "2"},
+      {"batch", "int", "median model: this many independent trials trial .. trial+batch-1 in one batched context "
+       "(gs_create_batch; one line per trial)", "0", false, "0"},
       {"blind", "bool", "rumor model: a hot node loses interest without waiting for a reply (GS_RUMOR_BLIND)",
        "false", false, "false"},
       {"coin", "bool", "rumor model: lose interest with probability 1/k per event, not after k events (GS_RUMOR_COIN)",
@@ -252,6 +256,23 @@ int main(int argc, char** argv) {
   if (model == "median" && ival("trials") > 1) {
     fprintf(stderr, "flag -trials %s with -model median: the median-counter model runs one trial on one device "
             "(GS_MODEL_MEDIAN)\n", find("trials")->val.c_str());
+    usage();
+    return 2;
+  }
+  const bool median_batch = find("batch")->given;
+  if (median_batch && model != "median") {
+    fprintf(stderr, "flag -batch needs -model median (it runs a batch of median-counter trials)\n");
+    usage();
+    return 2;
+  }
+  if (median_batch && (ival("batch") < 1 || ival("batch") > 0x7FFFFFFFll)) {
+    fprintf(stderr, "invalid value \"%s\" for flag -batch: want at least 1\n", find("batch")->val.c_str());
+    usage();
+    return 2;
+  }
+  if (median_batch && ival("gpus") > 1) {
+    fprintf(stderr, "flag -batch with -gpus %s: a median batch runs on one device (GS_MODEL_MEDIAN)\n",
+            find("gpus")->val.c_str());
     usage();
     return 2;
   }
@@ -302,7 +323,7 @@ int main(int argc, char** argv) {
     p.rumor_mode = rumor_mode;
   }
   const uint64_t max_ticks = (uint64_t)ival("maxticks");
-  const long long ntrials = ival("trials");
+  const long long ntrials = median_batch ? ival("batch") : ival("trials");
   if (ntrials < 1 || ntrials > 0x7FFFFFFFll) {
     fprintf(stderr, "invalid value \"%s\" for flag -trials: want at least 1\n", find("trials")->val.c_str());
     usage();
@@ -322,6 +343,8 @@ int main(int argc, char** argv) {
     rc = gs_create_multi(&p, devs.data(), (int)gpus, &c);
   } else if (p.model == GS_MODEL_RUMOR && p.trials > 1) {
     rc = gs_create_trials(&p, &c);  // gs_create keeps refusing the combination
+  } else if (median_batch) {
+    rc = gs_create_batch(&p, &c);  // the other creates keep refusing a median batch
   } else {
     rc = gs_create(&p, &c);
   }
@@ -377,33 +400,58 @@ int main(int argc, char** argv) {
     rc = gs_trial_results(c, tr.data(), tr.size(), &ntr);
     if (rc) return die(c, rc, "gs_trial_results");
     uint32_t got99 = 0;
-    if (p.model == GS_MODEL_RUMOR) {  // the model's own outputs per trial, then their statistics
+    if (p.model == GS_MODEL_RUMOR || median_batch) {  // the model's own outputs per trial, then their statistics
       static const char* const names[] = {"covered", "quiescent", "maxticks"};
       const size_t T = std::min(ntr, tr.size());
-      double sum[3] = {0, 0, 0}, sq[3] = {0, 0, 0};
+      // a median batch: the stranded nodes, those still active (B or C) at the trial's stop.  A trial
+      // that ended by itself has none and gets none later, and the others all stop at the run's last
+      // poll, so the state bytes at the end of the run give every trial's count.
+      std::vector<uint64_t> stranded(T, 0);
+      if (median_batch) {
+        std::vector<uint8_t> stb((size_t)p.trials * p.n);
+        rc = gs_read_median_state(c, stb.data(), stb.size());
+        if (rc) return die(c, rc, "gs_read_median_state");
+        for (size_t i = 0; i < T; ++i)
+          for (uint64_t v = 0; v < p.n; ++v) {
+            const uint8_t b = stb[i * p.n + v];
+            stranded[i] += b != 0 && b != 255;
+          }
+      }
+      const int F = median_batch ? 4 : 3;
+      double sum[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
       uint32_t ended = 0;
+      auto figures = [&](size_t i, double* x) {
+        x[0] = 1.0 - (double)tr[i].received / (double)p.n;
+        x[1] = (double)tr[i].messages / (double)p.n;
+        x[2] = (double)tr[i].tick;
+        x[3] = (double)stranded[i];
+      };
       for (size_t i = 0; i < T; ++i) {
         char rb[64], mb[64];
         gs_format_float32(1.0f - (float)tr[i].received / (float)p.n, rb, sizeof(rb));
         gs_format_float32((float)tr[i].messages / (float)p.n, mb, sizeof(mb));
-        printf("trial %" PRIu64 ": Residue %s, %s messages per node after %s, %s\n", tr[i].trial, rb, mb,
+        printf("trial %" PRIu64 ": Residue %s, %s messages per node after %s, %s", tr[i].trial, rb, mb,
                dur_ms(tr[i].tick).c_str(), names[tr[i].status >= 0 && tr[i].status <= 2 ? tr[i].status : 2]);
-        const double x[3] = {1.0 - (double)tr[i].received / (double)p.n, (double)tr[i].messages / (double)p.n,
-                             (double)tr[i].tick};
-        for (int f = 0; f < 3; ++f) sum[f] += x[f];
+        if (median_batch) printf(", stranded %" PRIu64, stranded[i]);
+        printf("\n");
+        double x[4];
+        figures(i, x);
+        for (int f = 0; f < F; ++f) sum[f] += x[f];
         if (tr[i].status != GS_RUN_MAX_TICKS) ++ended;
       }
-      double mean[3], sd[3];
-      for (int f = 0; f < 3; ++f) mean[f] = T ? sum[f] / (double)T : 0.0;
+      double mean[4], sd[4];
+      for (int f = 0; f < F; ++f) mean[f] = T ? sum[f] / (double)T : 0.0;
       for (size_t i = 0; i < T; ++i) {  // two passes: the deviations from the mean
-        const double x[3] = {1.0 - (double)tr[i].received / (double)p.n, (double)tr[i].messages / (double)p.n,
-                             (double)tr[i].tick};
-        for (int f = 0; f < 3; ++f) sq[f] += (x[f] - mean[f]) * (x[f] - mean[f]);
+        double x[4];
+        figures(i, x);
+        for (int f = 0; f < F; ++f) sq[f] += (x[f] - mean[f]) * (x[f] - mean[f]);
       }
-      for (int f = 0; f < 3; ++f) sd[f] = T > 1 ? std::sqrt(sq[f] / (double)(T - 1)) : 0.0;
-      printf("--- %zu trials: residue mean %s sd %s, messages per node mean %s sd %s, rounds mean %s sd %s ---\n", T,
+      for (int f = 0; f < F; ++f) sd[f] = T > 1 ? std::sqrt(sq[f] / (double)(T - 1)) : 0.0;
+      printf("--- %zu trials: residue mean %s sd %s, messages per node mean %s sd %s, rounds mean %s sd %s", T,
              gofloat(mean[0]).c_str(), gofloat(sd[0]).c_str(), gofloat(mean[1]).c_str(), gofloat(sd[1]).c_str(),
              gofloat(mean[2]).c_str(), gofloat(sd[2]).c_str());
+      if (median_batch) printf(", stranded mean %s sd %s", gofloat(mean[3]).c_str(), gofloat(sd[3]).c_str());
+      printf(" ---\n");
       fflush(stdout);
       const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
       fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, %u broadcasts %.3f s\n", ov_wall, p.trials, wall);

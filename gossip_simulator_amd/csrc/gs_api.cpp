@@ -7,7 +7,8 @@
 //   batched  one device, `trials` independent trials laid out at trial << tlog
 //            and run at once (config C3): the flood model by the window engine,
 //            push-pull by the trial-resident kernel (a workgroup per trial), the
-//            rumor model by its own (gs_create_trials only)
+//            rumor model by its own (gs_create_trials only), the median model by
+//            its own (gs_create_batch only)
 //   shard    one node range [lo, hi) of one broadcast (config C4): a member of a
 //            group, or one rank of a multi-process run (RCCL inside)
 //   group    gs_create_multi: shards or trial batches over several devices
@@ -193,6 +194,40 @@ int gs_create_trials(const gs_params* params, gs_ctx** out) {
   return create_one(params, params ? params->device : 0, false, 1, 0, out, true);
 }
 
+// gs_create_trials with the median / trials refusal lifted too: every other
+// check of the parameters still runs before any device call.
+int gs_create_batch(const gs_params* params, gs_ctx** out) {
+  g_create_err.clear();
+  if (!out) return GS_EINVAL;
+  *out = nullptr;
+  return create_one(params, params ? params->device : 0, false, 1, 0, out, true, true);
+}
+
+int gs_median_trials_max_n(int device, uint64_t* n_max) {
+  g_create_err.clear();
+  if (!n_max) return GS_EINVAL;
+  *n_max = 0;
+  int ndev = 0;
+  std::string why;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess) {
+    why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
+  } else if (device < 0 || device >= ndev) {
+    why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
+  } else {
+    uint64_t lim = 0;
+    why = mdt_limit_error(device, &lim);
+    if (why.empty()) {
+      *n_max = mdt_max_n(lim);
+      return GS_OK;
+    }
+  }
+  (void)hipGetLastError();
+  fprintf(stderr, "gs_median_trials_max_n: %s\n", why.c_str());
+  g_create_err = why;
+  return GS_EDEVICE;
+}
+
 int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max) {
   g_create_err.clear();
   if (!n_max) return GS_EINVAL;
@@ -359,6 +394,11 @@ int gs_load_peers_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32
   if (!c || !d_deg || !d_ids || stride < 2 || stride > 255)
     return fail(c, GS_EINVAL, "bad device peer table (stride must be in [2,255])");
   if (c->begun) return fail(c, GS_EINVAL, "peers must be loaded before gs_broadcast_begin");
+  if (c->mdt) {  // a median batch: tables back to back, as gs_load_peers takes them
+    RC(mdt_load_device(c, d_deg, d_ids, stride));
+    c->peers = true;
+    return GS_OK;
+  }
   if (c->group || c->trials > 1)
     return fail(c, GS_EINVAL, "device tables load into one-device, one-trial contexts");
   CK(c, hipSetDevice(c->dev));

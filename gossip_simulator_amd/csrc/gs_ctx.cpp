@@ -15,7 +15,7 @@ uint32_t ceil_log2(uint64_t x) {
   return b;
 }
 
-int check_params(const gs_params* p, bool rumor_trials, std::string& why) {
+int check_params(const gs_params* p, bool rumor_trials, bool median_trials, std::string& why) {
   if (!p) { why = "params is NULL"; return GS_EINVAL; }
   if (p->n == 0) { why = "n must be >= 1 (simulator.go:240 panics on rand.Intn(0))"; return GS_EINVAL; }
   if (p->n > 0x7FFFFFFFull) { why = "n must be < 2^31"; return GS_EINVAL; }
@@ -36,7 +36,7 @@ int check_params(const gs_params* p, bool rumor_trials, std::string& why) {
     why = "GS_MODEL_MEDIAN needs 1 <= rumor_k <= 127, not " + std::to_string(p->rumor_k);
     return GS_EINVAL;
   }
-  if (p->model == GS_MODEL_MEDIAN && p->trials > 1) {
+  if (p->model == GS_MODEL_MEDIAN && p->trials > 1 && !median_trials) {
     why = "GS_MODEL_MEDIAN with trials > 1: the median-counter model runs one trial per context";
     return GS_EINVAL;
   }
@@ -266,7 +266,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
   c->win = !c->pp && !c->rumor && !c->median && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
-  if (((c->trials > 1 && !c->ppt && !c->rmt) || (shard && !c->pp)) && !c->win) {
+  if (((c->trials > 1 && !c->ppt && !c->rmt && !c->mdt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
           "fanout/fanin <= 32, no GS_FLAG_TICK_ENGINE, at most 2^30 nodes per context or shard)";
     return GS_EINVAL;
@@ -351,7 +351,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
     pt.kd = s.kd;
     pt.key = s.key;
   }
-  if (c->rmt && !alloc_trial_rows(c, (size_t)c->trials * kMaxWindow * kTStatFields * 4, 0)) {
+  if ((c->rmt || c->mdt) && !alloc_trial_rows(c, (size_t)c->trials * kMaxWindow * kTStatFields * 4, 0)) {
     why = "cannot allocate the per-trial counters";
     return GS_ENOMEM;
   }
@@ -723,15 +723,21 @@ int ppt_masked_plan(const gs_ctx* c, PptPlan* plan, std::string& why) {
 thread_local std::string g_create_err;
 
 int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
-               bool rumor_trials) {
+               bool rumor_trials, bool median_trials) {
   std::string why;
   PptPlan pl;
   RmtPlan rpl;
-  int rc = check_params(params, rumor_trials, why);
+  MdtPlan mpl;
+  int rc = check_params(params, rumor_trials, median_trials, why);
   if (!rc) rc = check_ppt_n(params, device, why, &pl);
   if (!rc) rc = check_rmt_n(params, device, why, &rpl);
+  if (!rc) rc = check_mdt_n(params, device, why, &mpl);
   if (!rc) {
     gs_ctx* c = new gs_ctx();
+    if (mpl.block) {  // batched median trials: the plan check_mdt_n made for this device
+      c->mdt = true;
+      c->mplan = mpl;
+    }
     if (rpl.block) {  // batched rumor trials: the plan check_rmt_n made for this device
       c->rmt = true;
       c->rplan = rpl;

@@ -20,6 +20,7 @@
 #include "gossip.h"
 #include "gs_comm.h"
 #include "gs_internal.h"
+#include "gs_mdt_plan.h"
 #include "gs_median.h"
 #include "gs_ppt_plan.h"
 #include "gs_rmt_plan.h"
@@ -117,9 +118,11 @@ struct RumorBufs {
 // median-counter push-pull (gs_median.hip): the state bytes [n], the
 // own-contribution bytes [n], the tally [n] u64, the gotb / gotc bitsets [W],
 // round control (a RumorCtl) and, once gs_read_removed asks, the done bitset
-// [W]: median_alloc / release_median
+// [W].  A batched context (gs_median_trials.hip) has the state bytes over the
+// padded id space and the done bitset only: median_alloc / release_median
 struct MedianBufs {
   Buf st, own, tally, gotb, gotc, ctlb, done;
+  std::vector<uint32_t> actn;  // batched: every trial's active nodes after the last round run
   uint32_t grid = 0;  // the round kernel's persistent grid (median_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
 };
@@ -229,6 +232,9 @@ struct gs_ctx {
   // median-counter push-pull (gs_median.hip)
   bool median = false;
   gs::MedianBufs md;
+  // batched median trials (gs_create_batch; gs_median_trials.hip): a workgroup per trial
+  bool mdt = false;
+  gs::MdtPlan mplan{};
   // window engine (gs_win_*.hip)
   bool win = false;
   gs::WinState ws{};
@@ -346,9 +352,11 @@ constexpr uint32_t kSlots = 4;  // staging slots of the device-driven windows
 // gs_ctx.cpp
 extern thread_local std::string g_create_err;
 // rumor_trials: GS_MODEL_RUMOR with trials > 1 makes a batched rumor context
-// (gs_create_trials); every other create refuses the combination
+// (gs_create_trials, gs_create_batch); median_trials: GS_MODEL_MEDIAN with
+// trials > 1 makes a batched median context (gs_create_batch); every other
+// create refuses the combinations
 int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
-               bool rumor_trials = false);
+               bool rumor_trials = false, bool median_trials = false);
 int create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out);
 int finish_rank(gs_ctx* c, gs_ctx** out);
 void destroy_one(gs_ctx* c);
@@ -435,5 +443,8 @@ int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out,
                int32_t* status);
 int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
 int median_read_state(gs_ctx* c, uint8_t* st, size_t n);
+std::string mdt_limit_error(int device, uint64_t* lim);
+int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl);
+int mdt_load_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32_t stride);
 
 }  // namespace gs

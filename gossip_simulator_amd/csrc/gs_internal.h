@@ -232,8 +232,10 @@ constexpr uint32_t kStampPhases = 10;
 constexpr uint32_t kXStamp0 = 2 * kStampPhases;  // k_expand phases (GS_XSTAMPS builds) after k_resolve's
 constexpr uint32_t kDbgWords = kXStamp0 + 8;
 // per-trial window counters (batched trials)
-// (TS_HOT: batched rumor trials only -- the trial's hot nodes after the round)
-enum TStat : uint32_t { TS_FIRED = 0, TS_SENT = 1, TS_DEAD = 2, TS_RECV = 3, TS_CRASH = 4, TS_HOT = 5 };
+// (TS_HOT: batched rumor trials -- the trial's hot nodes after the round -- and
+// batched median trials -- its active nodes; TS_MSGS: batched median trials only
+// -- the active ends of the round's connections)
+enum TStat : uint32_t { TS_FIRED = 0, TS_SENT = 1, TS_DEAD = 2, TS_RECV = 3, TS_CRASH = 4, TS_HOT = 5, TS_MSGS = 6 };
 constexpr uint32_t kTStatFields = 8;
 
 // Key (node, counter word 3) of global id g for a draw of `kind`.
@@ -607,6 +609,39 @@ hipError_t rmt_prepare(int device, uint32_t mode, uint32_t lds_bytes);
 hipError_t rmt_seed(const RmtState& s, uint32_t node, uint32_t* started, hipStream_t st);
 // Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
 hipError_t rmt_rounds(const RmtState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
+
+// Batched median-counter trials (gs_median_trials.hip; DESIGN.md section
+// 4.8.1): one workgroup per trial, the trial's state bytes, signed tallies and
+// flag sets in LDS (plan: gs_mdt_plan.h), up to kMaxWindow rounds per launch.
+// Nodes at trial << tlog | v as in every batched context.  Between launches
+// the state bytes live in global memory, in the trial's own slot.
+struct MdtState {
+  const uint8_t* deg;
+  const uint32_t* ids;
+  unsigned long long* recv;         // [(trials << tlog) / 64] informed words, rebuilt from st at every store
+  uint8_t* st;                      // [trials << tlog] state bytes between launches (gs_median.h's encoding)
+  const unsigned long long* crash;  // per-trial failure masks, laid out like recv (null: none)
+  uint32_t* tstat;                  // [trials][kMaxWindow][kTStatFields] per-round counters of every trial
+  uint32_t n, trials, tlog, stride;
+  uint32_t block, lds_bytes;        // MdtPlan of n on this device
+  uint32_t k;                       // gs_params.rumor_k, 1..127
+  int32_t kd;
+  Key key;
+};
+// Per-workgroup LDS the device grants k_mdt_rounds (bytes).  On an error
+// *where (may be null) names the HIP call that failed.
+hipError_t mdt_lds_limit(int device, uint64_t* limit, const char** where = nullptr);
+// Opt both instantiations (masked and not) in to lds_bytes > 64 KiB of dynamic LDS on `device`.
+hipError_t mdt_prepare(int device, uint32_t lds_bytes);
+// Every trial's sender (`node`, or ~0u: the trial's keyed sender) B-1 unless
+// failed; st zeroed by the caller.  started[trial] = 1 if it was informed.
+hipError_t mdt_seed(const MdtState& s, uint32_t node, uint32_t* started, hipStream_t st);
+// Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
+hipError_t mdt_rounds(const MdtState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
+// Device tables back to back (ids local to their trial) into the zeroed padded
+// id space; *err: 1 = a row longer than the stride, 2 = a friend id >= n.
+hipError_t mdt_spread_table(const uint8_t* deg, const uint32_t* ids, uint32_t n, uint32_t trials, uint32_t tlog,
+                            uint32_t stride, uint8_t* odeg, uint32_t* oids, uint32_t* err, hipStream_t st);
 
 // Launchers (gs_broadcast.hip).
 hipError_t launch_tick(const DevState& st, uint32_t tick, int mode, hipStream_t s);

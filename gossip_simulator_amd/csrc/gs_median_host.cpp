@@ -1,7 +1,8 @@
 // gs_median_host.cpp -- the host side of median-counter push-pull
 // (GS_MODEL_MEDIAN): its buffers, the round loop and
 // gs_run's stop rule.  One trial on one device (the kernels are in
-// gs_median.hip).
+// gs_median.hip), or a batch of trials, a workgroup each (gs_create_batch;
+// gs_median_trials.hip).
 #include "gs_ctx.h"
 
 namespace gs {
@@ -29,13 +30,247 @@ void median_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, bool 
   if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
 }
 
+// ---- batched trials --------------------------------
+
+MdtState mdt_state(const gs_ctx* c) {
+  MdtState m{};
+  m.deg = c->st.deg;
+  m.ids = c->st.ids;
+  m.recv = c->st.recv;
+  m.st = (uint8_t*)c->md.st.p;
+  m.crash = c->failed ? c->st.crash : nullptr;
+  m.tstat = c->bt.d_tstat;
+  m.n = (uint32_t)c->p.n;
+  m.trials = c->trials;
+  m.tlog = c->tlog;
+  m.stride = c->st.stride;
+  m.block = c->mplan.block;
+  m.lds_bytes = (uint32_t)c->mplan.lds_bytes;
+  m.k = c->p.rumor_k;
+  m.kd = c->st.kd;
+  m.key = c->st.key;
+  return m;
+}
+
+// Every trial's sender (k_mdt_seed): the trials that started have one informed,
+// active node.  The started flags use the first words of the counter rows,
+// free between broadcasts.
+int mdt_begin(gs_ctx* c, uint64_t sender) {
+  CK(c, hipSetDevice(c->dev));
+  const uint32_t T = c->trials;
+  const MdtState ms = mdt_state(c);
+  CK(c, hipMemsetAsync(c->md.st.p, 0, c->st.n, c->stream));
+  CK(c, mdt_seed(ms, (uint32_t)sender, c->bt.d_tstat, c->stream));
+  CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  c->recv = c->pending = 0;
+  for (uint32_t tr = 0; tr < T; ++tr) {
+    c->md.actn[tr] = c->bt.h_tstat[tr];
+    c->tacc[tr].start = c->tacc[tr].recv = c->bt.h_tstat[tr];
+    c->recv += c->tacc[tr].recv;
+    c->pending += c->md.actn[tr];
+  }
+  c->begun = true;
+  return GS_OK;
+}
+
+// `ticks` rounds of every trial, at most kMaxWindow per launch (rmt_step's
+// loop); out[k] = the sum of the trials' rows, pending = their active nodes.
+// tick_99 is taken at polls only (median_account's rule).
+int mdt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  CK(c, hipSetDevice(c->dev));
+  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
+  const MdtState ms = mdt_state(c);
+  const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
+  while (timing && c->ev.size() < 2) {
+    hipEvent_t ev;
+    CK(c, hipEventCreate(&ev));
+    c->ev.push_back(ev);
+  }
+  uint32_t done = 0;
+  while (done < ticks) {
+    const uint32_t batch = std::min<uint32_t>(ticks - done, kMaxWindow);
+    const uint64_t t0 = c->t + 1;
+    if (timing) CK(c, hipEventRecord(c->ev[0], c->stream));
+    CK(c, mdt_rounds(ms, (uint32_t)t0, batch, c->stream));
+    if (timing) CK(c, hipEventRecord(c->ev[1], c->stream));
+    CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, tb, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    if (timing) {
+      float ms_ = 0;
+      CK(c, hipEventElapsedTime(&ms_, c->ev[0], c->ev[1]));
+      c->timing.deliver_ms += ms_;  // the rounds kernel: `batch` rounds of every trial
+      c->timing.deliver_launches++;
+    }
+    for (uint32_t k = 0; k < batch; ++k) {
+      const bool poll = every_tick_polls || done + k + 1 == ticks;
+      unsigned long long fired = 0, sent = 0, msgs = 0, act = 0;
+      for (uint32_t tr = 0; tr < c->trials; ++tr) {
+        const uint32_t* r = c->bt.h_tstat + ((size_t)tr * kMaxWindow + k) * kTStatFields;
+        TrialAcc& a = c->tacc[tr];
+        a.fired += r[TS_FIRED];
+        a.sent += r[TS_SENT];
+        a.msgs += r[TS_MSGS];
+        a.recv += r[TS_RECV];
+        if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = t0 + k;
+        c->md.actn[tr] = r[TS_HOT];
+        fired += r[TS_FIRED];
+        sent += r[TS_SENT];
+        msgs += r[TS_MSGS];
+        c->recv += r[TS_RECV];
+        act += r[TS_HOT];
+      }
+      c->t = t0 + k;
+      c->fired += fired;
+      c->sent += sent;
+      c->msgs += msgs;
+      c->pending = act;
+      if (out) out[done + k] = gs_tick_stats{c->t, fired, sent, msgs, c->recv, 0, c->pending};
+    }
+    done += batch;
+  }
+  return GS_OK;
+}
+
+// median_run's rule per trial: a trial stops at the first poll at which it has
+// no active node (covered or quiescent by the float32 rule at that poll), else
+// at max_ticks; the run ends when all have stopped.
+int mdt_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+            int32_t* status) {
+  size_t k = 0;
+  int32_t st = GS_RUN_MAX_TICKS;
+  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
+  for (;;) {
+    RC(mdt_step(c, poll, nullptr, false));
+    if (out && k < cap)
+      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
+    ++k;
+    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
+    uint32_t running = 0;
+    for (uint32_t tr = 0; tr < c->trials; ++tr) {
+      TrialAcc& a = c->tacc[tr];
+      if (a.status != GS_RUN_RUNNING) continue;
+      if (c->md.actn[tr] == 0) snap_trial(c, tr, covered(a.recv, c->p.n) ? GS_RUN_COVERED : GS_RUN_QUIESCENT);
+      else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);
+      else ++running;
+    }
+    if (trials_stopped(c, running, &st)) break;
+  }
+  if (nout) *nout = k;
+  if (status) *status = st;
+  return GS_OK;
+}
+
+// The D set of every trial, built from the state bytes over the padded id
+// space (padding bytes are 0); trials x ceil(n/64) words, trial-major.
+int mdt_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
+  const uint64_t Wn = (c->p.n + 63) / 64;
+  if (!words || nwords < Wn * c->trials) return fail(c, GS_EINVAL, "need ceil(n/64) words per trial");
+  CK(c, hipSetDevice(c->dev));
+  if (!grow(c->md.done, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the done set");
+  unsigned long long* d = (unsigned long long*)c->md.done.p;
+  MedianState m{};
+  m.st = (uint8_t*)c->md.st.p;
+  if (c->begun) CK(c, median_done_set(c->st, m, d, c->stream));
+  else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));  // (st is the last run's: nothing is informed)
+  CK(c, hipMemcpy2DAsync(words, Wn * 8, d, ((size_t)1 << c->tlog) / 8, Wn * 8, c->trials, hipMemcpyDeviceToHost,
+                         c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
+// trials * n bytes, trial-major, without the padding of the internal layout.
+int mdt_read_state(gs_ctx* c, uint8_t* st, size_t n) {
+  const size_t need = (size_t)c->trials * c->p.n;
+  if (!st || n < need) return fail(c, GS_EINVAL, "need trials * n bytes (trial-major)");
+  CK(c, hipSetDevice(c->dev));
+  if (!c->begun) {  // (st is the last run's: every node is uninformed)
+    memset(st, 0, need);
+    return GS_OK;
+  }
+  CK(c, hipMemcpy2DAsync(st, c->p.n, c->md.st.p, (size_t)1 << c->tlog, c->p.n, c->trials, hipMemcpyDeviceToHost,
+                         c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
 }  // namespace
 
-// The combinations the model does not run: every create but gs_create.
+// mdt_lds_limit with its failure in words ("" on success), as rmt_limit_error.
+std::string mdt_limit_error(int device, uint64_t* lim) {
+  const char* where = "";
+  const hipError_t e = mdt_lds_limit(device, lim, &where);
+  if (e == hipSuccess) return std::string();
+  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
+         std::to_string((int)e) + ")";
+}
+
+// Batched median trials (gs_create_batch): n is bounded by what `device`
+// grants one workgroup (gs_mdt_plan.h), so it is validated with the other
+// parameters, after check_params and before any device state is set up; *pl
+// gets the plan (block 0: not such a context).  With no device to ask the
+// parameters were valid as far as they can be checked: GS_EDEVICE.
+int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl) {
+  *pl = MdtPlan{};
+  if (p->trials <= 1 || p->model != GS_MODEL_MEDIAN) return GS_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    why = "no HIP device visible (libgossip_hip needs an MI355X)";
+    return GS_EDEVICE;
+  }
+  if (device < 0 || device >= ndev) {
+    why = "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)";
+    return GS_EDEVICE;
+  }
+  uint64_t lim = 0;
+  why = mdt_limit_error(device, &lim);
+  if (!why.empty()) {
+    (void)hipGetLastError();
+    return GS_EDEVICE;
+  }
+  const MdtPlan plan = mdt_plan(p->n, lim);
+  if (!plan.fits) {
+    why = "batched median trials keep a trial's state bytes, tallies and flag sets in one workgroup's LDS: n must "
+          "be <= " + std::to_string(mdt_max_n(lim)) + " on this device (gs_median_trials_max_n), not " +
+          std::to_string(p->n) + "; a one-trial context (gs_create) has no such limit";
+    return GS_EINVAL;
+  }
+  if (plan.lds_bytes > 65536 && mdt_prepare(device, (uint32_t)plan.lds_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    why = "cannot raise the trial-resident median kernel's dynamic LDS limit";
+    return GS_EDEVICE;
+  }
+  *pl = plan;
+  return GS_OK;
+}
+
+// gs_load_peers_device on a batch: the trials' tables back to back in device
+// memory, spread into the padded id space and validated on the device.
+int mdt_load_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32_t stride) {
+  CK(c, hipSetDevice(c->dev));
+  c->row_slots = 0;
+  RC(alloc_table(c, stride));
+  CK(c, hipMemsetAsync(c->d_deg, 0, c->ntot, c->stream));
+  CK(c, hipMemsetAsync(c->d_ids, 0, c->ntot * stride * 4ull, c->stream));
+  CK(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
+  CK(c, mdt_spread_table((const uint8_t*)d_deg, (const uint32_t*)d_ids, (uint32_t)c->p.n, c->trials, c->tlog, stride,
+                         c->d_deg, c->d_ids, c->d_err, c->stream));
+  uint32_t e = 0;
+  CK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  CK(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
+  if (e & 1) return fail(c, GS_EINVAL, "a friends-list length exceeds the row stride");
+  if (e & 2) return fail(c, GS_EINVAL, "a friend id is >= n");
+  return seal_rows(c, c->d_deg, c->d_ids, c->ntot);
+}
+
+// The combinations the model does not run: every create but gs_create and
+// gs_create_batch.
 int median_refuse(const gs_params* params, const char* what) {
   if (!params || params->model != GS_MODEL_MEDIAN) return GS_OK;
   g_create_err = std::string(what) + " with GS_MODEL_MEDIAN: the median-counter model runs one trial on one device "
-                 "(gs_create)";
+                 "(gs_create), or a batch of trials through gs_create_batch";
   fprintf(stderr, "%s: %s\n", what, g_create_err.c_str());
   return GS_EINVAL;
 }
@@ -43,10 +278,16 @@ int median_refuse(const gs_params* params, const char* what) {
 // Nothing of the flood's window buffers, push-pull's reverse table or the
 // rumor model's lists: the state bytes, the own-contribution bytes, the tally
 // and two bitsets.  At n = 1e9: 1 + 1 + 8 GB and 2 x 125 MB, from the block
-// cache like every buffer of 64 MiB or more.
+// cache like every buffer of 64 MiB or more.  A batched context keeps the
+// rest in LDS: the state bytes over the padded id space only.
 int median_alloc(gs_ctx* c) {
   const uint64_t n = c->st.n;
   MedianBufs& b = c->md;
+  if (c->mdt) {
+    if (!grow(b.st, n)) return fail(c, GS_ENOMEM, "cannot allocate the batched median trials' state bytes");
+    b.actn.assign(c->trials, 0);
+    return GS_OK;
+  }
   if (!grow(b.st, n) || !grow(b.own, n) || !grow(b.tally, n * 8) || !grow(b.gotb, c->st.W * 8) ||
       !grow(b.gotc, c->st.W * 8) || !grow(b.ctlb, sizeof(RumorCtl)) ||
       hipHostMalloc((void**)&b.h_ctl, sizeof(RumorCtl)) != hipSuccess)
@@ -64,6 +305,7 @@ void release_median(gs_ctx* c) {
 // A live sender becomes B-1 (received = 1, as in push-pull); a failed one
 // starts nothing and the first poll is quiescent.
 int median_begin(gs_ctx* c, uint64_t sender) {
+  if (c->mdt) return mdt_begin(c, sender);
   CK(c, hipSetDevice(c->dev));
   // GS_MEDIAN_GRID: the round kernel's blocks (read per broadcast, so tests can
   // make a short table take several passes of the grid)
@@ -89,6 +331,7 @@ int median_begin(gs_ctx* c, uint64_t sender) {
 // every_tick_polls: each tick is a poll (gs_step returns every tick's row);
 // else only the call's last tick is (gs_run).
 int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  if (c->mdt) return mdt_step(c, ticks, out, every_tick_polls);
   CK(c, hipSetDevice(c->dev));
   const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
   const MedianState ms = median_state(c);
@@ -144,6 +387,7 @@ int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_p
 int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
                int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
+  if (c->mdt) return mdt_run(c, poll, max_ticks, out, cap, nout, status);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
@@ -164,6 +408,7 @@ int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out,
 
 // removed = the D set, built from the state bytes.
 int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
+  if (c->mdt) return mdt_read_removed(c, words, nwords);
   if (!words || nwords < c->st.W) return fail(c, GS_EINVAL, "need ceil(n/64) words");
   CK(c, hipSetDevice(c->dev));
   if (!grow(c->md.done, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the done set");
@@ -177,6 +422,7 @@ int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
 
 int median_read_state(gs_ctx* c, uint8_t* st, size_t n) {
   if (!c->median) return fail(c, GS_EINVAL, "gs_read_median_state needs a GS_MODEL_MEDIAN context");
+  if (c->mdt) return mdt_read_state(c, st, n);
   if (!st || n < c->p.n) return fail(c, GS_EINVAL, "need n bytes");
   CK(c, hipSetDevice(c->dev));
   if (!c->begun) {  // (st is the last run's: every node is uninformed)

@@ -38,7 +38,8 @@ class Config:
     model: str = "flood"    # "flood" (the reference), "pushpull" (extension),
                             # "rumor" (extension, DESIGN.md 4.7: one device; a batch of trials
                             # through Simulator.batch) or "median" (extension, DESIGN.md 4.8:
-                            # median-counter push-pull, one trial on one device)
+                            # median-counter push-pull, one trial on one device; a batch of
+                            # trials through Simulator.median_batch)
     rumor_k: int = 2        # rumor: a node stops calling after this many calls that reached an
                             # informed peer (1..255); median: the counter steps and the rounds of
                             # the final phase (1..127)
@@ -46,7 +47,8 @@ class Config:
     rumor_coin: bool = False   # rumor: an event removes with probability 1/rumor_k (GS_RUMOR_COIN)
     rumor_pull: bool = False   # rumor: every live node calls; hot nodes answer (GS_RUMOR_PULL)
     trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3): flood and
-                            # push-pull through Simulator(cfg), every model through Simulator.batch(cfg)
+                            # push-pull through Simulator(cfg), the rumor model too through
+                            # Simulator.batch(cfg), every model through Simulator.median_batch(cfg)
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
                               # rounds bottom-up once |I| >= 96n/256), "dense" (every round streams the
@@ -110,7 +112,10 @@ class Simulator:
     (entries may repeat), or the trials split over them when cfg.trials > 1.
     Simulator.rank(...): one rank of a multi-process run (gs_create_rank).
     Simulator.batch(cfg): gs_create_trials -- as Simulator(cfg), and also a
-    batch of rumor trials (model="rumor", trials > 1), which gs_create refuses."""
+    batch of rumor trials (model="rumor", trials > 1), which gs_create refuses.
+    Simulator.median_batch(cfg): gs_create_batch -- as Simulator.batch(cfg), and
+    also a batch of median trials (model="median", trials > 1), which both
+    other creates refuse."""
 
     def __init__(self, cfg: Config, devices=None, _rank=None, _batch=False):
         self.cfg = cfg
@@ -131,6 +136,9 @@ class Simulator:
             devs = (C.c_int * len(devices))(*[int(d) for d in devices])
             rc = self.L.gs_create_multi(C.byref(self._p), devs, len(devices), C.byref(h))
             what = "gs_create_multi"
+        elif _batch == "median":
+            rc = self.L.gs_create_batch(C.byref(self._p), C.byref(h))
+            what = "gs_create_batch"
         elif _batch:
             rc = self.L.gs_create_trials(C.byref(self._p), C.byref(h))
             what = "gs_create_trials"
@@ -154,6 +162,15 @@ class Simulator:
         the batched layouts: tables back to back, one mask per trial,
         [trials, ceil(n/64)] sets."""
         return cls(cfg, _batch=True)
+
+    @classmethod
+    def median_batch(cls, cfg: Config):
+        """cfg.trials trials at once on cfg.device through gs_create_batch: what
+        Simulator.batch(cfg) makes, and for model="median" with trials > 1 a
+        batched median context (n <= median_trials_max_n(); the default n =
+        50,000 does not fit: use Simulator(cfg) per trial there).  Every call
+        takes the batched layouts, and median_state() is [trials, n]."""
+        return cls(cfg, _batch="median")
 
     @classmethod
     def rank(cls, cfg: Config, nranks: int, rank: int, comm_id: bytes | None):
@@ -328,12 +345,13 @@ class Simulator:
         return w if self.trials == 1 else w.reshape(self.trials, self.words)
 
     def median_state(self) -> np.ndarray:
-        """Median model: every node's state byte, [n] uint8: 0 = uninformed, m in
-        1..rumor_k = informed with counter m, rumor_k + c = round c of the final
-        phase, 255 = done (gs_read_median_state)."""
-        st = np.zeros(self.n, dtype=np.uint8)
+        """Median model: every node's state byte, [n] uint8 (a median_batch of
+        trials: [trials, n]): 0 = uninformed, m in 1..rumor_k = informed with
+        counter m, rumor_k + c = round c of the final phase, 255 = done
+        (gs_read_median_state)."""
+        st = np.zeros(self.n * self.trials, dtype=np.uint8)
         self._check(self.L.gs_read_median_state(self.h, st.ctypes.data, st.size), "gs_read_median_state")
-        return st
+        return st if self.trials == 1 else st.reshape(self.trials, self.n)
 
     def trial_results(self) -> np.ndarray:
         """[trials, len(TRIAL_FIELDS)] int64: per trial its number, first
@@ -443,6 +461,20 @@ def rumor_trials_max_n(mode=0, device: int = 0) -> int:
     if rc != 0:
         why = L.gs_last_error(None).decode(errors="replace")
         raise GossipError(rc, "gs_rumor_trials_max_n failed" + (f" ({why})" if why and why != "NULL context" else ""))
+    return int(out.value)
+
+
+def median_trials_max_n(device: int = 0) -> int:
+    """Largest n a batched median context (Simulator.median_batch,
+    model="median", trials > 1) may have on `device`
+    (gs_median_trials_max_n): the trial's state bytes, tallies and flag sets
+    live in one workgroup's LDS."""
+    L = _lib.load()
+    out = C.c_uint64(0)
+    rc = L.gs_median_trials_max_n(int(device), C.byref(out))
+    if rc != 0:
+        why = L.gs_last_error(None).decode(errors="replace")
+        raise GossipError(rc, "gs_median_trials_max_n failed" + (f" ({why})" if why and why != "NULL context" else ""))
     return int(out.value)
 
 

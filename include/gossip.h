@@ -107,7 +107,10 @@ enum {
                               * informed node that nobody connects to, or whose partners are all
                               * done already, stays B, so such a run ends GS_RUN_MAX_TICKS (a
                               * short counter strands some nodes this way: DESIGN.md section 4.8).
-                              * One trial on one device: trials > 1,
+                              * One trial on one device through gs_create; gs_create_batch is the
+                              * batch of trials (one workgroup per trial, the trial's state in LDS,
+                              * so n <= gs_median_trials_max_n()).  The
+                              * four other creates keep refusing: gs_create with trials > 1,
                               * gs_create_trials, gs_create_multi and gs_create_rank[_exchange]
                               * answer GS_EINVAL */
 
@@ -340,6 +343,39 @@ int gs_create_trials(const gs_params* params, gs_ctx** out);
  * A failure mask does not lower it.  GS_EINVAL for a bad mode bit, GS_EDEVICE
  * where the device cannot be asked. */
 int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max);
+/* gs_create_trials with one more refusal lifted: GS_MODEL_MEDIAN with
+ * params.trials > 1 makes a batched median context on params.device, trials
+ * params.trial .. params.trial + trials - 1 run at once, a workgroup each.
+ * Every other parameter set is handled exactly as by gs_create_trials (median
+ * with trials <= 1: the one-trial context of gs_create).  It is a third create
+ * for the reason given above: gs_create and gs_create_trials have always
+ * answered GS_EINVAL for a median batch, programs test for that answer, and
+ * they keep giving it.  Every parameter check runs before any device call
+ * (rumor_k 1..127, the 31-bit id space, n >= 1): bad parameters answer
+ * GS_EINVAL with the reason in gs_last_error(NULL) even where no device is
+ * visible, valid ones then answer GS_EDEVICE.  n past gs_median_trials_max_n()
+ * answers GS_EINVAL and names the limit (about 31,000 on an MI355X: the
+ * reference's default n = 50,000 does not fit; use a one-trial context there).
+ * The batched context takes the usual calls with the batched layouts
+ * (gs_load_peers and gs_load_peers_device: tables back to back;
+ * gs_build_overlay: the batch's own overlays; gs_set_failed: one mask per
+ * trial; gs_broadcast_begin: a fixed node in every trial, or < 0 each trial's
+ * keyed sender; gs_step rows: sums over the trials, pending = their active
+ * nodes; gs_read_received / _crashed / _removed: trials x ceil(n/64) words,
+ * trial-major; gs_read_median_state: trials x n bytes, trial-major).  Trial i
+ * behaves exactly like a one-trial gs_create context with params.trial + i,
+ * trial i's table and trial i's mask, round by round, also in rounds stepped
+ * after its own end.  gs_run: each trial stops at the first poll at which it
+ * has no active node (GS_RUN_COVERED or GS_RUN_QUIESCENT by the float32 rule
+ * at that poll) or at max_ticks; the run ends when all have stopped, with the
+ * latest status among them. */
+int gs_create_batch(const gs_params* params, gs_ctx** out);
+/* Largest n a batched median context may have on `device`: a state byte and a
+ * signed tally word per node and two bitsets (336 B per 64 nodes) must fit the
+ * LDS the device grants one workgroup.  gs_create_batch refuses a larger n
+ * with GS_EINVAL.  A failure mask does not lower it.  GS_EDEVICE where the
+ * device cannot be asked. */
+int gs_median_trials_max_n(int device, uint64_t* n_max);
 
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
@@ -347,7 +383,8 @@ int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max);
  * (deg[trials*n], ids[trials*n*stride], ids local to their trial).  A sharded
  * context keeps only each shard's partition (gs_read_peers then fails). */
 int gs_load_peers(gs_ctx* ctx, const uint8_t* deg, const uint32_t* ids, uint32_t stride);
-/* Same, from device-resident buffers (copied device-to-device). */
+/* Same, from device-resident buffers (copied device-to-device).  One-trial
+ * contexts, and a gs_create_batch median batch (tables back to back). */
 int gs_load_peers_device(gs_ctx* ctx, const void* d_deg, const void* d_ids, uint32_t stride);
 /* Copies the current table out (stride = max(fanout, fanin) after an overlay). */
 int gs_read_peers(gs_ctx* ctx, uint8_t* deg, uint32_t* ids, uint32_t* stride_out);
@@ -418,8 +455,9 @@ int gs_read_removed(gs_ctx* ctx, uint64_t* words, size_t nwords);
 /* GS_MODEL_MEDIAN: every node's state byte, st[n]: 0 = uninformed (A), m in
  * 1..rumor_k = informed with counter m (B-m), rumor_k + c = round c of the final
  * phase (C-c, c in 1..rumor_k), 255 = done (D).  gs_read_received gives the
- * nodes whose byte is not 0, gs_read_removed those at 255.  GS_EINVAL on a
- * context of another model. */
+ * nodes whose byte is not 0, gs_read_removed those at 255.  A gs_create_batch
+ * batch: trials x n bytes, trial-major (a shorter buffer: GS_EINVAL).
+ * GS_EINVAL on a context of another model. */
 int gs_read_median_state(gs_ctx* ctx, uint8_t* st, size_t n);
 
 int gs_timing_get(gs_ctx* ctx, gs_timing* out);
