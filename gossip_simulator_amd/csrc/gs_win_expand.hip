@@ -469,15 +469,19 @@ uint32_t win_expand_geometry(const WinState& w, uint64_t Tn, uint32_t* per_round
   const uint64_t rounds = (Tn + per_round - 1) / per_round;
   // rows <= 8 slots: a persistent grid of four workgroups per CU (the LDS
   // holds four) whatever the window's size -- a sparse window then costs one
-  // wave of workgroups, not several (GS_XGRID: A/B knob).  Longer rows (the
-  // 20- and 32-slot instances fit more workgroups per CU): up to 8192.
-  static const uint64_t cap = [] {
+  // wave of workgroups, not several.  Longer rows (the 20- and 32-slot
+  // instances fit more workgroups per CU): up to 8192.  GS_XGRID=<workgroups
+  // of 256 threads> (A/B knob, at least 8; 0 = unset) replaces both caps, so
+  // tests can make a workgroup run several rounds of a small window; it stays
+  // in here, where plan_coarse_trials sees the same grid.
+  static const uint64_t xgrid = [] {
     const char* e = getenv("GS_XGRID");
-    return e ? (uint64_t)std::max(atoi(e), 8) : (uint64_t)device_cus() * 4;
+    return e ? (uint64_t)std::max(atoi(e), 8) : 0ull;
   }();
+  const uint64_t cap = rs > 8 ? (xgrid ? xgrid : 8192) : (xgrid ? xgrid : (uint64_t)device_cus() * 4) * kExpandBlock / bsz;
   // (a thread counts fired | sent << 16 of its nodes in 16-bit halves: at most
   // 1024 rounds per workgroup, <= 4096 nodes and 32768 sends per thread)
-  const uint64_t grid_cap = std::max<uint64_t>(rs <= 8 ? cap * kExpandBlock / bsz : 8192, (rounds + 1023) / 1024);
+  const uint64_t grid_cap = std::max<uint64_t>(cap, (rounds + 1023) / 1024);
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(rounds, grid_cap);
   if (per_round_out) *per_round_out = per_round;
   if (bsz_out) *bsz_out = bsz;

@@ -335,9 +335,21 @@ hipError_t win_plan(const WinState& w, bool exact, hipStream_t s) {
   return hipGetLastError();
 }
 
+// GS_PART2_GRID=<workgroups> (read once per process; 0 = unset): the grid of
+// every k_part2 launch, the guarded redo's count and scatter included, so
+// tests can make a workgroup take several tiles of a small window.  A multiple
+// of 8 keeps the tiles dealt by XCD; any other value strides the whole list.
+static uint32_t part2_grid_env() {
+  static const uint32_t g = [] { const char* e = getenv("GS_PART2_GRID"); return e ? (uint32_t)std::max(atoi(e), 1) : 0u; }();
+  return g;
+}
+// the guarded redo's count and scatter grids
+static uint32_t redo_grid() { return part2_grid_env() ? part2_grid_env() : 512u; }
+
 hipError_t win_part2(const WinState& w, uint64_t T, bool scatter, hipStream_t s) {
   const uint64_t tiles = (T + kPartTile - 1) / kPartTile + 256;
-  const uint32_t blocks = (uint32_t)(std::min<uint64_t>(tiles, 8192) + 7) & ~7u;  // a multiple of 8: tiles by XCD
+  uint32_t blocks = (uint32_t)(std::min<uint64_t>(tiles, 8192) + 7) & ~7u;  // a multiple of 8: tiles by XCD
+  if (part2_grid_env()) blocks = part2_grid_env();
   if (scatter) hipLaunchKernelGGL(k_part2<true>, dim3(blocks), dim3(kPartBlock), 0, s, w);
   else hipLaunchKernelGGL(k_part2<false>, dim3(blocks), dim3(kPartBlock), 0, s, w);
   return hipGetLastError();
@@ -355,9 +367,9 @@ hipError_t win_fine_redo(const WinState& w, uint64_t /*T*/, hipStream_t s) {  //
   // only reads the control block and leaves
   hipLaunchKernelGGL(k_fine_zero, dim3(64), dim3(256), 0, s, g);
   hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, s, g, true);
-  hipLaunchKernelGGL(k_part2<false>, dim3(512), dim3(kPartBlock), 0, s, g);
+  hipLaunchKernelGGL(k_part2<false>, dim3(redo_grid()), dim3(kPartBlock), 0, s, g);
   hipLaunchKernelGGL(k_fine_scan, dim3(1), dim3(1024), 0, s, g);
-  hipLaunchKernelGGL(k_part2<true>, dim3(512), dim3(kPartBlock), 0, s, g);
+  hipLaunchKernelGGL(k_part2<true>, dim3(redo_grid()), dim3(kPartBlock), 0, s, g);
   return hipGetLastError();
 }
 
@@ -365,15 +377,16 @@ hipError_t win_recv_g(const WinGroup& g, uint64_t T, hipStream_t s) {
   const uint32_t pblocks = std::min<uint32_t>((g.nfine_max + 1 + 255) / 256, 1024);
   hipLaunchKernelGGL(k_plan_m, dim3(pblocks, g.M), dim3(256), 0, s, g.wr, false);
   const uint64_t tiles = (T + kPartTile - 1) / kPartTile + 256;
-  const uint32_t blocks = (uint32_t)(std::min<uint64_t>(tiles, 8192) + 7) & ~7u;
+  uint32_t blocks = (uint32_t)(std::min<uint64_t>(tiles, 8192) + 7) & ~7u;
+  if (part2_grid_env()) blocks = part2_grid_env();
   hipLaunchKernelGGL(k_part2_m<true>, dim3(blocks, g.M), dim3(kPartBlock), 0, s, g.wr);
   // the guarded exact redo (win_fine_redo): each launch leaves at once unless
   // its shard's fine regions overflowed
   hipLaunchKernelGGL(k_fine_zero_m, dim3(64, g.M), dim3(256), 0, s, g.wg);
   hipLaunchKernelGGL(k_plan_m, dim3(1, g.M), dim3(256), 0, s, g.wg, true);
-  hipLaunchKernelGGL(k_part2_m<false>, dim3(512, g.M), dim3(kPartBlock), 0, s, g.wg);
+  hipLaunchKernelGGL(k_part2_m<false>, dim3(redo_grid(), g.M), dim3(kPartBlock), 0, s, g.wg);
   hipLaunchKernelGGL(k_fine_scan_m, dim3(g.M), dim3(1024), 0, s, g.wg);
-  hipLaunchKernelGGL(k_part2_m<true>, dim3(512, g.M), dim3(kPartBlock), 0, s, g.wg);
+  hipLaunchKernelGGL(k_part2_m<true>, dim3(redo_grid(), g.M), dim3(kPartBlock), 0, s, g.wg);
   return hipGetLastError();
 }
 

@@ -1023,6 +1023,15 @@ static bool resolve_occ3() {
   return on;
 }
 
+// GS_RESOLVE_GRID=<workgroups> (read once per process; 0 = unset): the
+// persistent grid of k_resolve / k_resolve2 and their _m twins (per shard),
+// so tests can make one workgroup own several buckets of a small table.  The
+// kResolveMaxBuckets bound still holds.
+static uint32_t resolve_grid_env() {
+  static const uint32_t g = [] { const char* e = getenv("GS_RESOLVE_GRID"); return e ? (uint32_t)std::max(atoi(e), 1) : 0u; }();
+  return g;
+}
+
 hipError_t win_resolve(const WinState& w, uint32_t t0, uint32_t L, hipStream_t s) {
   // persistent, each workgroup owning <= 256 buckets.  k_resolve: three
   // resident per CU, six queued (the second three even out the first three's
@@ -1032,7 +1041,7 @@ hipError_t win_resolve(const WinState& w, uint32_t t0, uint32_t L, hipStream_t s
   const bool occ3 = resolve_occ3();
   static const uint32_t per_cu_env = [] { const char* e = getenv("GS_RESOLVE_PER_CU"); return e ? (uint32_t)std::max(atoi(e), 1) : 0u; }();  // A/B knob
   const uint32_t per_cu = per_cu_env ? per_cu_env : occ3 ? 6u : 2u;
-  uint32_t G = std::min<uint32_t>(w.nfine, per_cu * cus);
+  uint32_t G = std::min<uint32_t>(w.nfine, resolve_grid_env() ? resolve_grid_env() : per_cu * cus);
   G = std::max<uint32_t>(G, (w.nfine + kResolveMaxBuckets - 1) / kResolveMaxBuckets);
   const uint32_t gs = (w.nfine + kSmallBlock / 64 - 1) / (kSmallBlock / 64);
   hipLaunchKernelGGL(k_resolve_small<false>, dim3(gs), dim3(kSmallBlock), 0, s, w, t0, L);
@@ -1054,7 +1063,8 @@ hipError_t win_resolve_g(const WinGroup& g, uint32_t L, hipStream_t s) {
   // k_resolve's resident workgroups per CU split over the shards (each still
   // owns <= kResolveMaxBuckets buckets of its shard)
   const bool occ3 = resolve_occ3();
-  uint32_t G = std::min<uint32_t>(g.nfine_max, ((occ3 ? 3 : 2) * cus + g.M - 1) / g.M);
+  uint32_t G = std::min<uint32_t>(g.nfine_max,
+                                  resolve_grid_env() ? resolve_grid_env() : ((occ3 ? 3 : 2) * cus + g.M - 1) / g.M);
   G = std::max<uint32_t>(G, (g.nfine_max + kResolveMaxBuckets - 1) / kResolveMaxBuckets);
   const uint32_t gs = (g.nfine_max + kSmallBlock / 64 - 1) / (kSmallBlock / 64);
   hipLaunchKernelGGL(k_resolve_small_m<false>, dim3(gs, g.M), dim3(kSmallBlock), 0, s, g.wr, L);
