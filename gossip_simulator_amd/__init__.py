@@ -15,6 +15,8 @@ Layers:
                             the pull variants: a dense engine over bitsets
   csrc/gs_rumor_trials.hip  batched rumor trials: a workgroup per trial, state in LDS, every mode
                             dense over bitsets (plan: gs_rmt_plan.h)
+  csrc/gs_rumorset.hip      concurrent push-pull rumors (gs_create_rumorset): up to 64 broadcasts over
+                            one table in one pass, a bit per rumor in a u64 per node; a dense engine
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI entry points: argument checks, dispatch by context kind
   csrc/gs_ctx.h, gs_ctx.cpp the context behind the ABI: set-up and release of every kind
@@ -23,6 +25,7 @@ Layers:
   csrc/gs_shards.cpp        host side of flood node-range shards and their exchanges
   csrc/gs_pushpull_host.cpp host side of push-pull: sparse rounds, shards, batched trials
   csrc/gs_rumor_host.cpp    host side of rumor mongering: buffers, round loop, stop rule
+  csrc/gs_rumorset_host.cpp host side of a rumor set: refusals, buffers, round loop, per-rumor results
   csrc/gs_devmem.cpp        process-wide cache of large device blocks (gs_trim)
   csrc/gossip_sim.cpp       CLI with the reference's flags and stdout
   engine.py                 Python host API (ctypes)

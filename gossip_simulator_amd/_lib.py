@@ -27,6 +27,7 @@ GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR, GS_MODEL_MEDIAN = 0, 1, 2, 3
 GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL = 1, 2, 4
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
 GS_COMM_ID_BYTES = 128
+GS_RUMORSET_MAX = 64
 
 # Every symbol include/gossip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -41,6 +42,8 @@ EXPORTS = (
     "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
     "gs_create_trials", "gs_rumor_trials_max_n", "gs_read_median_state",
     "gs_create_batch", "gs_median_trials_max_n",
+    "gs_create_rumorset", "gs_rumorset_begin", "gs_rumorset_results", "gs_read_rumorset",
+    "gs_read_rumor_column",
 )
 
 
@@ -83,6 +86,11 @@ class TrialStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in
                 ("trial", "tick_99", "tick", "fired", "sent", "messages", "received", "crashed")] + \
         [("status", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class RumorStats(C.Structure):
+    _fields_ = [("sender", C.c_int64), ("received", C.c_uint64), ("tick_99", C.c_uint64),
+                ("started", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class Window(C.Structure):
@@ -174,6 +182,11 @@ def load():
         "gs_pp_trials_max_n_masked": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_rumor_trials_max_n": ([C.c_int, C.c_uint32, P(C.c_uint64)], C.c_int),
         "gs_median_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
+        "gs_create_rumorset": ([P(Params), C.c_uint32, P(vp)], C.c_int),
+        "gs_rumorset_begin": ([ctx, P(C.c_int64), sz], C.c_int),
+        "gs_rumorset_results": ([ctx, P(RumorStats), sz, P(sz)], C.c_int),
+        "gs_read_rumorset": ([ctx, vp, sz], C.c_int),
+        "gs_read_rumor_column": ([ctx, C.c_uint32, vp, sz], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -4,8 +4,11 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -trials -device -peers -maxticks -model -k -batch) are not echoed in
-// the parameter block, so stdout keeps the reference's shape.  -model rumor
+// (-seed -trial -trials -device -peers -maxticks -model -k -batch -rumors) are not echoed in
+// the parameter block, so stdout keeps the reference's shape.  -model pushpull
+// -rumors R runs R rumors from keyed senders as one rumor set
+// (gs_create_rumorset): each poll's line shows the least-covered started rumor,
+// then one line per rumor and the round at which all were covered.  -model rumor
 // and -model median run to their own end and add the residue and the messages
 // per node (-model median: one trial, or -batch T trials through
 // gs_create_batch, printed like the rumor model's with a stranded column: the
@@ -190,6 +193,60 @@ bool load_peers_file(const std::string& path, uint64_t n, std::vector<uint8_t>& 
   return ok;
 }
 
+// -rumors R: R push-pull broadcasts from keyed senders in one pass (DESIGN.md
+// section 4.9).  One gs_run per 10-ms poll, so that every poll's line can show
+// the least-covered started rumor; then one line per rumor and the round at
+// which all were covered.
+int run_rumor_set(gs_ctx* c, const gs_params& p, uint32_t R, uint64_t max_ticks, double ov_wall) {
+  printf("=== Broadcast %u rumors ===\n", R);
+  fflush(stdout);
+  const auto b0 = std::chrono::steady_clock::now();
+  int rc = gs_broadcast_begin(c, -1);  // every sender keyed
+  if (rc) return die(c, rc, "gs_broadcast_begin");
+  std::vector<gs_rumor_stats> rs(R);
+  size_t nrs = 0;
+  int32_t status = GS_RUN_MAX_TICKS;
+  gs_tick_stats tot{};
+  do {
+    gs_totals(c, &tot);
+    rc = gs_run(c, 10, std::min<uint64_t>(tot.tick + 10, max_ticks), nullptr, 0, nullptr, &status);  // one poll
+    if (rc) return die(c, rc, "gs_run");
+    rc = gs_rumorset_results(c, rs.data(), rs.size(), &nrs);
+    if (rc) return die(c, rc, "gs_rumorset_results");
+    gs_totals(c, &tot);
+    uint64_t least = p.n;
+    bool any = false;
+    for (uint32_t j = 0; j < R; ++j)
+      if (rs[j].started) {
+        least = std::min<uint64_t>(least, rs[j].received);
+        any = true;
+      }
+    char pb[64];
+    gs_format_float32((any ? (float)least / (float)p.n : 0.0f) * 100.0f, pb, sizeof(pb));
+    printf("%s%% covered, took %s\n", pb, dur_ms(tot.tick).c_str());
+  } while (status == GS_RUN_MAX_TICKS && tot.tick < max_ticks);
+  for (uint32_t j = 0; j < R; ++j) {
+    printf("rumor %u: sender %" PRId64 ", %" PRIu64 " nodes, ", j, rs[j].sender, rs[j].received);
+    if (!rs[j].started) printf("never started (its sender is failed)\n");
+    else if (rs[j].tick_99) printf("99%% after %s\n", dur_ms(rs[j].tick_99).c_str());
+    else printf("99%% not reached\n");
+  }
+  const double bc_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
+  if (status != GS_RUN_COVERED) {
+    fflush(stdout);
+    fprintf(stderr, "%s: %s before every rumor reached 99%% coverage\n", g_prog,
+            status == GS_RUN_QUIESCENT ? "no rumor started" : "-maxticks reached");
+    gs_destroy(c);
+    return 3;
+  }
+  printf("--- Took %s to get 99%% of all %u rumors ---\n\n", dur_ms(tot.tick).c_str(), R);
+  printf("Total message %" PRIu64 " Total Crashed %" PRIu64 "\n", tot.messages, tot.crashed);
+  fflush(stdout);
+  fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, %u rumors %.3f s\n", ov_wall, R, bc_wall);
+  gs_destroy(c);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -225,6 +282,8 @@ int main(int argc, char** argv) {
        "false", false, "false"},
       {"pull", "bool", "rumor model: every node calls and hot nodes answer (GS_RUMOR_PULL)", "false", false,
        "false"},
+      {"rumors", "int", "pushpull model: this many rumors, 1..64, from keyed senders over one table in one pass "
+       "(gs_create_rumorset; one line per rumor)", "0", false, "0"},
       {"maxticks", "int", "give up after this many simulated ms per phase", "10000000", false,
        "10000000"},
   };
@@ -273,6 +332,22 @@ int main(int argc, char** argv) {
   if (median_batch && ival("gpus") > 1) {
     fprintf(stderr, "flag -batch with -gpus %s: a median batch runs on one device (GS_MODEL_MEDIAN)\n",
             find("gpus")->val.c_str());
+    usage();
+    return 2;
+  }
+  const bool rumor_set = find("rumors")->given;
+  if (rumor_set && model != "pushpull") {
+    fprintf(stderr, "flag -rumors needs -model pushpull (it runs concurrent push-pull rumors)\n");
+    usage();
+    return 2;
+  }
+  if (rumor_set && (ival("rumors") < 1 || ival("rumors") > (long long)GS_RUMORSET_MAX)) {
+    fprintf(stderr, "invalid value \"%s\" for flag -rumors: want 1..64\n", find("rumors")->val.c_str());
+    usage();
+    return 2;
+  }
+  if (rumor_set && (ival("trials") > 1 || ival("gpus") > 1)) {
+    fprintf(stderr, "flag -rumors with -trials or -gpus above 1: a rumor set runs one trial on one device\n");
     usage();
     return 2;
   }
@@ -345,6 +420,8 @@ int main(int argc, char** argv) {
     rc = gs_create_trials(&p, &c);  // gs_create keeps refusing the combination
   } else if (median_batch) {
     rc = gs_create_batch(&p, &c);  // the other creates keep refusing a median batch
+  } else if (rumor_set) {
+    rc = gs_create_rumorset(&p, (uint32_t)ival("rumors"), &c);  // the only way in to a rumor set
   } else {
     rc = gs_create(&p, &c);
   }
@@ -382,6 +459,7 @@ int main(int argc, char** argv) {
   printf("--- Took %s to stabilize ---\n\n", dur_ms(stab).c_str()); // :235
   const double ov_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
 
+  if (rumor_set) return run_rumor_set(c, p, (uint32_t)ival("rumors"), max_ticks, ov_wall);
   printf("=== Broadcast one message ===\n");                    // :237
   fflush(stdout);
   const auto b0 = std::chrono::steady_clock::now();

@@ -12,6 +12,8 @@
 //   shard    one node range [lo, hi) of one broadcast (config C4): a member of a
 //            group, or one rank of a multi-process run (RCCL inside)
 //   group    gs_create_multi: shards or trial batches over several devices
+// A rumor set (gs_create_rumorset) is a plain context with an engine of its own
+// (gs_rumorset_host.cpp): up to 64 push-pull broadcasts in one pass.
 #include "gs_ctx.h"
 
 using namespace gs;
@@ -201,6 +203,44 @@ int gs_create_batch(const gs_params* params, gs_ctx** out) {
   if (!out) return GS_EINVAL;
   *out = nullptr;
   return create_one(params, params ? params->device : 0, false, 1, 0, out, true, true);
+}
+
+// The only way in to a rumor set: the other creates keep every answer they give.
+int gs_create_rumorset(const gs_params* params, uint32_t rumors, gs_ctx** out) {
+  g_create_err.clear();
+  if (!out) return GS_EINVAL;
+  *out = nullptr;
+  RC(rs_check_create(params, rumors));
+  return create_one(params, params->device, false, 1, 0, out, false, false, rumors);
+}
+
+int gs_rumorset_begin(gs_ctx* c, const int64_t* senders, size_t count) {
+  if (!c) return GS_EINVAL;
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_rumorset_begin needs a gs_create_rumorset context");
+  if (!c->peers) return fail(c, GS_EINVAL, "load peers or build the overlay first");
+  if (c->begun) return fail(c, GS_EINVAL, "broadcast already begun");
+  if (!senders || count != c->rumors)
+    return fail(c, GS_EINVAL, "the set has " + std::to_string(c->rumors) + " rumors: count must equal it");
+  for (size_t j = 0; j < count; ++j)
+    if (senders[j] >= 0 && (uint64_t)senders[j] >= c->p.n)
+      return fail(c, GS_EINVAL, "sender " + std::to_string(j) + " out of range");
+  reset_counters(c);
+  return rs_begin(c, senders);
+}
+
+int gs_rumorset_results(gs_ctx* c, gs_rumor_stats* out, size_t cap, size_t* nout) {
+  if (!c) return GS_EINVAL;
+  return rs_results(c, out, cap, nout);
+}
+
+int gs_read_rumorset(gs_ctx* c, uint64_t* have, size_t n) {
+  if (!c) return GS_EINVAL;
+  return rs_read_words(c, have, n);
+}
+
+int gs_read_rumor_column(gs_ctx* c, uint32_t rumor, uint64_t* words, size_t nwords) {
+  if (!c) return GS_EINVAL;
+  return rs_read_column(c, rumor, words, nwords);
 }
 
 int gs_median_trials_max_n(int device, uint64_t* n_max) {
@@ -509,6 +549,11 @@ int gs_broadcast_begin(gs_ctx* c, int64_t sender) {
   if (c->begun) return fail(c, GS_EINVAL, "broadcast already begun");
   if (sender >= 0 && (uint64_t)sender >= c->p.n) return fail(c, GS_EINVAL, "sender out of range");
   reset_counters(c);
+  if (c->rset) {  // every sender keyed, or rumor j at (sender + j) mod n
+    int64_t snd[kRsMax];
+    for (uint32_t j = 0; j < c->rumors; ++j) snd[j] = sender < 0 ? -1 : (int64_t)(((uint64_t)sender + j) % c->p.n);
+    return rs_begin(c, snd);
+  }
   if (c->group && c->gtrials) {
     for (gs_ctx* m : c->gr.mem) {
       if (gs_broadcast_begin(m, sender)) return fail(c, GS_EINVAL, m->err);
@@ -620,6 +665,7 @@ int gs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out) {
   }
   if (c->rumor) return rumor_step(c, ticks, out, true);
   if (c->median) return median_step(c, ticks, out, true);
+  if (c->rset) return rs_step(c, ticks, out, true);
   if (c->pp && (c->group || c->pp_shard)) return pp_shard_step(c, ticks, out);
   if (c->group) return shard_step(c, c->gr.mem, ticks, out);
   if (c->shard) return abort_rank(c, shard_step(c, {c}, ticks, out));
@@ -651,6 +697,7 @@ int gs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, siz
   }
   if (c->rumor) return rumor_run(c, poll, max_ticks, out, cap, nout, status);
   if (c->median) return median_run(c, poll, max_ticks, out, cap, nout, status);
+  if (c->rset) return rs_run(c, poll, max_ticks, out, cap, nout, status);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   const bool trials = c->trials > 1 && !c->group;
@@ -786,12 +833,15 @@ int gs_read_crashed(gs_ctx* c, uint64_t* words, size_t nwords) {
 
 int gs_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   if (!c) return GS_EINVAL;
+  if (c->rset) return fail(c, GS_EINVAL, "gs_read_removed: a rumor set removes nobody (every node calls every round)");
   if (c->median) return median_read_removed(c, words, nwords);
   return rumor_read_removed(c, words, nwords);
 }
 
 int gs_read_median_state(gs_ctx* c, uint8_t* st, size_t n) {
   if (!c) return GS_EINVAL;
+  if (c->rset)
+    return fail(c, GS_EINVAL, "gs_read_median_state needs a GS_MODEL_MEDIAN context (a rumor set: gs_read_rumorset)");
   return median_read_state(c, st, n);
 }
 

@@ -208,7 +208,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   c->stream = c->own;
   DevState& s = c->st;
   const uint32_t stride0 = (uint32_t)std::max(c->p.fanout, c->p.fanin);
-  c->pp = c->p.model == GS_MODEL_PUSHPULL;
+  c->pp = c->p.model == GS_MODEL_PUSHPULL && !c->rset;  // (a rumor set has its own engine and buffers)
   c->rumor = c->p.model == GS_MODEL_RUMOR;
   c->median = c->p.model == GS_MODEL_MEDIAN;
   c->pp_l2_only = (c->p.flags & GS_FLAG_PP_L2_ONLY) != 0;
@@ -264,7 +264,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // Engine: the window engine unless the ring is too long for LDS, rows are
   // wider than 32 or the tick engine is forced; push-pull has its own kernels.
   // (its coarse partition has 256 bins of 2^22 nodes: at most 2^30 nodes per context)
-  c->win = !c->pp && !c->rumor && !c->median && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
+  c->win = !c->pp && !c->rumor && !c->median && !c->rset && s.R <= kWinMaxRing && !(c->p.flags & GS_FLAG_TICK_ENGINE) && stride0 <= kWinMaxStride &&
            s.n <= (1ull << (kCoarseShift + 8));
   if (((c->trials > 1 && !c->ppt && !c->rmt && !c->mdt) || (shard && !c->pp)) && !c->win) {
     why = "batched trials and node-range shards run on the window engine (delayhigh <= 256, "
@@ -283,7 +283,7 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   // One state allocation, 256-B aligned sub-buffers; everything before
   // `stats` is per-broadcast state that gs_reset clears.
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const bool tick = !c->win && !c->pp && !c->rumor && !c->median;
+  const bool tick = !c->win && !c->pp && !c->rumor && !c->median && !c->rset;
   // (batched push-pull trials build `next` in LDS: no second bitset, no summaries;
   // the rumor model has the second bitset and no summaries, its batched trials neither)
   const size_t b_sum = c->pp && !c->ppt ? al(pp_summary_total_words(s.W) * 8) : 0;
@@ -333,6 +333,10 @@ int ctx_setup(gs_ctx* c, const gs_params* params, int device, bool shard, uint32
   }
   if (c->median) {
     int rc = median_alloc(c);
+    if (rc) { why = c->err; return rc; }
+  }
+  if (c->rset) {
+    int rc = rs_alloc(c);
     if (rc) { why = c->err; return rc; }
   }
   if (c->ppt) {  // per-trial counter rows and the stall check's buffers
@@ -723,7 +727,7 @@ int ppt_masked_plan(const gs_ctx* c, PptPlan* plan, std::string& why) {
 thread_local std::string g_create_err;
 
 int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
-               bool rumor_trials, bool median_trials) {
+               bool rumor_trials, bool median_trials, uint32_t rumorset) {
   std::string why;
   PptPlan pl;
   RmtPlan rpl;
@@ -734,6 +738,8 @@ int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint
   if (!rc) rc = check_mdt_n(params, device, why, &mpl);
   if (!rc) {
     gs_ctx* c = new gs_ctx();
+    c->rset = rumorset != 0;  // a rumor set (gs_create_rumorset checked the rest)
+    c->rumors = rumorset;
     if (mpl.block) {  // batched median trials: the plan check_mdt_n made for this device
       c->mdt = true;
       c->mplan = mpl;
@@ -781,6 +787,7 @@ void destroy_one(gs_ctx* c) {
   release_sparse(c);
   release_rumor(c);
   release_median(c);
+  release_rumorset(c);
   release_async(c);
   release_dd(c);
   if (c->own) (void)hipStreamDestroy(c->own);

@@ -2,8 +2,8 @@
 // the error macros and the few host functions that cross the engine files
 // (gs_ctx.cpp lifetime, gs_peers.cpp tables, gs_windows.cpp / gs_shards.cpp
 // the flood engines, gs_pushpull_host.cpp push-pull, gs_rumor_host.cpp rumor
-// mongering, gs_median_host.cpp median-counter push-pull, gs_api.cpp the entry
-// points).
+// mongering, gs_median_host.cpp median-counter push-pull, gs_rumorset_host.cpp
+// concurrent push-pull rumors, gs_api.cpp the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 #include "gs_median.h"
 #include "gs_ppt_plan.h"
 #include "gs_rmt_plan.h"
+#include "gs_rumorset.h"
 
 namespace gs {
 
@@ -125,6 +126,21 @@ struct MedianBufs {
   std::vector<uint32_t> actn;  // batched: every trial's active nodes after the last round run
   uint32_t grid = 0;  // the round kernel's persistent grid (median_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
+};
+
+// concurrent push-pull rumors (gs_rumorset.hip): the rumor words have, next
+// and own [n] u64 each, the count ring [kStatSlots][kRsMax], round control
+// (RsCtl) and, once gs_read_rumor_column asks, a column bitset [W]:
+// rs_alloc / release_rumorset
+struct RsBufs {
+  Buf have, next, own, ring, ctlb, col;
+  uint32_t grid = 0;  // the persistent grid of the round and the commit (rs_begin)
+  RsCtl* h_ctl = nullptr;               // pinned copy of the control block, read once per poll
+  unsigned long long* h_ring = nullptr; // pinned copy of the count ring
+  int64_t sender[kRsMax] = {};          // where each rumor started (rs_begin)
+  uint64_t count[kRsMax] = {};          // nodes that hold each rumor, as of the last row read
+  uint64_t tick99[kRsMax] = {};         // first poll at which its float32 rule held, else 0
+  uint64_t live = 0;                    // bit j: rumor j started
 };
 
 // batched trials' per-trial counter rows (both models) and the push-pull
@@ -235,6 +251,10 @@ struct gs_ctx {
   // batched median trials (gs_create_batch; gs_median_trials.hip): a workgroup per trial
   bool mdt = false;
   gs::MdtPlan mplan{};
+  // concurrent push-pull rumors (gs_create_rumorset; gs_rumorset.hip): `rumors` bits per node
+  bool rset = false;
+  uint32_t rumors = 0;
+  gs::RsBufs rsb;
   // window engine (gs_win_*.hip)
   bool win = false;
   gs::WinState ws{};
@@ -355,8 +375,9 @@ extern thread_local std::string g_create_err;
 // (gs_create_trials, gs_create_batch); median_trials: GS_MODEL_MEDIAN with
 // trials > 1 makes a batched median context (gs_create_batch); every other
 // create refuses the combinations
+// rumorset: 1..kRsMax makes a rumor set of that many rumors (gs_create_rumorset)
 int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint32_t rank, gs_ctx** out,
-               bool rumor_trials = false, bool median_trials = false);
+               bool rumor_trials = false, bool median_trials = false, uint32_t rumorset = 0);
 int create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out);
 int finish_rank(gs_ctx* c, gs_ctx** out);
 void destroy_one(gs_ctx* c);
@@ -446,5 +467,17 @@ int median_read_state(gs_ctx* c, uint8_t* st, size_t n);
 std::string mdt_limit_error(int device, uint64_t* lim);
 int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl);
 int mdt_load_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32_t stride);
+
+// gs_rumorset_host.cpp
+int rs_check_create(const gs_params* params, uint32_t rumors);
+int rs_alloc(gs_ctx* c);
+void release_rumorset(gs_ctx* c);
+int rs_begin(gs_ctx* c, const int64_t* senders);
+int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls);
+int rs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+           int32_t* status);
+int rs_results(gs_ctx* c, gs_rumor_stats* out, size_t cap, size_t* nout);
+int rs_read_words(gs_ctx* c, uint64_t* have, size_t n);
+int rs_read_column(gs_ctx* c, uint32_t rumor, uint64_t* words, size_t nwords);
 
 }  // namespace gs

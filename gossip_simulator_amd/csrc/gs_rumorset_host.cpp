@@ -1,0 +1,235 @@
+// gs_rumorset_host.cpp -- the host side of concurrent push-pull rumors
+// (gs_create_rumorset): the create's refusals, the
+// buffers, the round loop, gs_run's stop rule and the per-rumor results.  One
+// device; the kernels are in gs_rumorset.hip.
+#include "gs_ctx.h"
+
+namespace gs {
+
+namespace {
+
+RsState rs_state(const gs_ctx* c) {
+  return RsState{(RsCtl*)c->rsb.ctlb.p, (unsigned long long*)c->rsb.have.p, (unsigned long long*)c->rsb.next.p,
+                 (unsigned long long*)c->rsb.own.p, (unsigned long long*)c->rsb.ring.p, c->rumors};
+}
+
+// One round's row and counts on the host.  Rumor j's tick_99 and the set's
+// (the first poll with no started rumor uncovered) are taken at polls only
+// (median_account's rule).
+void rs_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, const unsigned long long* counts, bool poll,
+                gs_tick_stats* o) {
+  RsBufs& b = c->rsb;
+  c->t = tick;
+  c->fired += s[ST_FIRED];
+  c->sent += s[ST_SENT];
+  c->msgs += s[ST_MSGS];
+  c->recv += s[ST_RECV];
+  c->pending = s[ST_SCHED];
+  for (uint32_t j = 0; j < c->rumors; ++j) {
+    b.count[j] = counts[j];
+    if (poll && ((b.live >> j) & 1) && !b.tick99[j] && covered(b.count[j], c->p.n)) b.tick99[j] = tick;
+  }
+  TrialAcc& a = c->tacc[0];
+  a.fired = c->fired; a.sent = c->sent; a.msgs = c->msgs; a.recv = c->recv;
+  if (poll && !a.tick99 && b.live && c->pending == 0) a.tick99 = tick;
+  if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
+}
+
+}  // namespace
+
+// What gs_create_rumorset refuses, before any device call.
+int rs_check_create(const gs_params* params, uint32_t rumors) {
+  std::string why;
+  if (!params) why = "params is NULL";
+  else if (params->model != GS_MODEL_PUSHPULL)
+    why = "gs_create_rumorset: model must be GS_MODEL_PUSHPULL, not " + std::to_string(params->model) +
+          " (a rumor set is push-pull's: the calls do not depend on who is informed)";
+  else if (rumors < 1 || rumors > GS_RUMORSET_MAX)
+    why = "gs_create_rumorset: rumors must be in 1..64 (a bit per rumor in a uint64 per node), not " +
+          std::to_string(rumors);
+  else if (params->trials > 1)
+    why = "gs_create_rumorset: trials must be 0 or 1, not " + std::to_string(params->trials) +
+          " (the rumors of a set share one trial's table and draws)";
+  else if (params->flags & ~GS_FLAG_TIMING)
+    why = "gs_create_rumorset: flags " + std::to_string(params->flags) +
+          " has a bit besides GS_FLAG_TIMING (a rumor set has one round kind and no tick engine)";
+  if (why.empty()) return GS_OK;
+  fprintf(stderr, "%s\n", why.c_str());
+  g_create_err = why;
+  return GS_EINVAL;
+}
+
+// Nothing of push-pull's reverse table, summaries or lists: three words per
+// node (24 GB at n = 1e9, from the block cache like every buffer of 64 MiB or
+// more), the count ring and the control block.
+int rs_alloc(gs_ctx* c) {
+  const uint64_t n = c->st.n;
+  RsBufs& b = c->rsb;
+  const size_t ring = (size_t)kStatSlots * kRsMax * 8;
+  if (!grow(b.have, n * 8) || !grow(b.next, n * 8) || !grow(b.own, n * 8) || !grow(b.ring, ring) ||
+      !grow(b.ctlb, sizeof(RsCtl)) || hipHostMalloc((void**)&b.h_ctl, sizeof(RsCtl)) != hipSuccess ||
+      hipHostMalloc((void**)&b.h_ring, ring) != hipSuccess)
+    return fail(c, GS_ENOMEM, "cannot allocate the rumor set's state");
+  return GS_OK;
+}
+
+// (col grows at the first gs_read_rumor_column)
+void release_rumorset(gs_ctx* c) {
+  RsBufs& b = c->rsb;
+  for (Buf* q : {&b.have, &b.next, &b.own, &b.ring, &b.ctlb, &b.col}) release(*q);
+  if (b.h_ctl) (void)hipHostFree(b.h_ctl);
+  if (b.h_ring) (void)hipHostFree(b.h_ring);
+}
+
+// senders[j] < 0: rumor j's keyed sender.  A failed sender starts nothing; if
+// none starts the first poll is quiescent.
+int rs_begin(gs_ctx* c, const int64_t* senders) {
+  CK(c, hipSetDevice(c->dev));
+  // GS_RUMORSET_GRID: the blocks of the round and the commit (read per
+  // broadcast, so tests can make a short table take several passes of the grid)
+  const char* e = getenv("GS_RUMORSET_GRID");
+  RsBufs& b = c->rsb;
+  b.grid = rs_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
+  RsSenders snd{};
+  for (uint32_t j = 0; j < c->rumors; ++j) {
+    snd.node[j] = senders[j] >= 0 ? (uint32_t)senders[j]
+                                  : uniform(draw0(c->st.key, K_SENDER, j, 0, 0), (uint32_t)c->p.n);
+    b.sender[j] = snd.node[j];
+    b.tick99[j] = 0;
+  }
+  CK(c, hipMemsetAsync(b.ctlb.p, 0, sizeof(RsCtl), c->stream));
+  for (Buf* q : {&b.have, &b.next, &b.own}) CK(c, hipMemsetAsync(q->p, 0, c->st.n * 8, c->stream));
+  CK(c, hipMemsetAsync(c->st.recv, 0, c->st.W * 8, c->stream));
+  CK(c, rs_seed(c->st, rs_state(c), snd, cover_threshold(c->p.n), c->stream));
+  CK(c, hipMemcpyAsync(b.h_ctl, b.ctlb.p, sizeof(RsCtl), hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  b.live = b.h_ctl->live;
+  for (uint32_t j = 0; j < kRsMax; ++j) b.count[j] = b.h_ctl->cnt[j];
+  c->recv = c->tacc[0].recv = b.h_ctl->received;
+  c->pending = b.h_ctl->pending;
+  c->begun = true;
+  return GS_OK;
+}
+
+// `ticks` rounds, three launches each, enqueued without a host sync between
+// them; the stats rows, the count ring's slots and the control block come back
+// once per call (per kStatSlots rounds).  every_tick_polls: each tick is a
+// poll (gs_step); else only the call's last tick is (gs_run).
+int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
+  CK(c, hipSetDevice(c->dev));
+  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
+  const RsState rs = rs_state(c);
+  RsBufs& b = c->rsb;
+  uint32_t done = 0;
+  while (done < ticks) {
+    const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
+    const uint64_t t0 = c->t + 1;
+    const StatSpans sp = stat_spans(t0, batch);
+    while (timing && c->ev.size() < (size_t)batch * 3) {
+      hipEvent_t ev;
+      CK(c, hipEventCreate(&ev));
+      c->ev.push_back(ev);
+    }
+    for (uint32_t i = 0; i < batch; ++i) {
+      const uint32_t tt = (uint32_t)(t0 + i);
+      hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
+      if (ev) CK(c, hipEventRecord(ev[0], c->stream));
+      CK(c, rs_round(c->st, rs, tt, b.grid, c->stream));
+      if (ev) CK(c, hipEventRecord(ev[1], c->stream));
+      CK(c, rs_commit(c->st, rs, tt, b.grid, c->stream));
+      if (ev) CK(c, hipEventRecord(ev[2], c->stream));
+    }
+    for (int j = 0; j < sp.n; ++j) {  // a ring slot is kRsMax words where a stats row is kStatFields
+      const size_t off = sp.off[j] / kStatFields * kRsMax, words = sp.words[j] / kStatFields * kRsMax;
+      CK(c, hipMemcpyAsync(c->h_stats + sp.off[j], c->st.stats + sp.off[j], sp.words[j] * 8, hipMemcpyDeviceToHost,
+                           c->stream));
+      CK(c, hipMemcpyAsync(b.h_ring + off, rs.ring + off, words * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    CK(c, hipMemcpyAsync(b.h_ctl, b.ctlb.p, sizeof(RsCtl), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < batch && timing; ++i) {
+      float ms_ = 0;
+      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3], c->ev[(size_t)i * 3 + 1]));
+      c->timing.deliver_ms += ms_;  // the round kernel
+      c->timing.deliver_launches++;
+      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3 + 1], c->ev[(size_t)i * 3 + 2]));
+      c->timing.resolve_ms += ms_;  // commit + publish
+      c->timing.resolve_launches++;
+    }
+    for (uint32_t i = 0; i < batch; ++i) {
+      const size_t slot = (size_t)((t0 + i) % kStatSlots);
+      const bool poll = every_tick_polls || done + i + 1 == ticks;
+      rs_account(c, t0 + i, c->h_stats + slot * kStatFields, b.h_ring + slot * kRsMax, poll,
+                 out ? &out[done + i] : nullptr);
+    }
+    if (b.h_ctl->received != c->recv || b.h_ctl->pending != c->pending)
+      return fail(c, GS_EDEVICE, "the rumor set's control block and the stats rows disagree");
+    done += batch;
+  }
+  return GS_OK;
+}
+
+// Stops at the first poll with no started rumor below 99 % (the device's stop
+// word: covered, or quiescent if no rumor started), or at max_ticks.  There
+// is no test for "nothing can change": a masked run that cannot reach 99 %
+// ends at max_ticks.
+int rs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+           int32_t* status) {
+  if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin or gs_rumorset_begin first");
+  size_t k = 0;
+  int32_t st = GS_RUN_MAX_TICKS;
+  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
+  for (;;) {
+    RC(rs_step(c, poll, nullptr, false));
+    if (out && k < cap)
+      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
+    ++k;
+    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
+    if (c->rsb.h_ctl->stop) { st = (int32_t)c->rsb.h_ctl->stop - 1; break; }
+    if (c->t >= max_ticks) break;
+  }
+  snap_trial(c, 0, st);
+  if (nout) *nout = k;
+  if (status) *status = st;
+  return GS_OK;
+}
+
+int rs_results(gs_ctx* c, gs_rumor_stats* out, size_t cap, size_t* nout) {
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_rumorset_results needs a gs_create_rumorset context");
+  const RsBufs& b = c->rsb;
+  for (uint32_t j = 0; j < c->rumors && out && j < cap; ++j) {
+    const bool on = c->begun && ((b.live >> j) & 1);
+    out[j] = gs_rumor_stats{c->begun ? b.sender[j] : -1, on ? b.count[j] : 0, on ? b.tick99[j] : 0, on ? 1 : 0, 0};
+  }
+  if (nout) *nout = c->rumors;
+  return GS_OK;
+}
+
+int rs_read_words(gs_ctx* c, uint64_t* have, size_t n) {
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_read_rumorset needs a gs_create_rumorset context");
+  if (!have || n < c->p.n) return fail(c, GS_EINVAL, "need n words");
+  CK(c, hipSetDevice(c->dev));
+  if (!c->begun) {  // (have is the last run's: nobody holds a rumor)
+    memset(have, 0, c->p.n * 8);
+    return GS_OK;
+  }
+  CK(c, hipMemcpyAsync(have, c->rsb.have.p, c->p.n * 8, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
+int rs_read_column(gs_ctx* c, uint32_t rumor, uint64_t* words, size_t nwords) {
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_read_rumor_column needs a gs_create_rumorset context");
+  if (rumor >= c->rumors) return fail(c, GS_EINVAL, "rumor must be below the set's " + std::to_string(c->rumors));
+  if (!words || nwords < c->st.W) return fail(c, GS_EINVAL, "need ceil(n/64) words");
+  CK(c, hipSetDevice(c->dev));
+  if (!grow(c->rsb.col, c->st.W * 8)) return fail(c, GS_ENOMEM, "cannot allocate the column bitset");
+  unsigned long long* d = (unsigned long long*)c->rsb.col.p;
+  if (c->begun) CK(c, rs_column(c->st, rs_state(c), rumor, d, c->stream));
+  else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));
+  CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipStreamSynchronize(c->stream));
+  return GS_OK;
+}
+
+}  // namespace gs

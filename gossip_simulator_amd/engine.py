@@ -117,12 +117,16 @@ class Simulator:
     also a batch of median trials (model="median", trials > 1), which both
     other creates refuse."""
 
-    def __init__(self, cfg: Config, devices=None, _rank=None, _batch=False):
+    def __init__(self, cfg: Config, devices=None, _rank=None, _batch=False, _rumors=None):
         self.cfg = cfg
         self.L = _lib.load()
         self._p = cfg.to_params()
+        self.rumors = 0 if _rumors is None else int(_rumors)
         h = C.c_void_p()
-        if _rank is not None and len(_rank) == 5:  # host exchange: (nranks, rank, all_gather, all_reduce, all_to_allv)
+        if _rumors is not None:
+            rc = self.L.gs_create_rumorset(C.byref(self._p), self.rumors, C.byref(h))
+            what = "gs_create_rumorset"
+        elif _rank is not None and len(_rank) == 5:  # host exchange: (nranks, rank, all_gather, all_reduce, all_to_allv)
             nranks, rank, ag, ar, av = _rank
             self._xfns = self._exchange_fns(nranks, ag, ar, av)  # kept alive with the context
             rc = self.L.gs_create_rank_exchange(C.byref(self._p), cfg.device, nranks, rank,
@@ -171,6 +175,17 @@ class Simulator:
         50,000 does not fit: use Simulator(cfg) per trial there).  Every call
         takes the batched layouts, and median_state() is [trials, n]."""
         return cls(cfg, _batch="median")
+
+    @classmethod
+    def rumor_set(cls, cfg: Config, rumors: int):
+        """`rumors` (1..64) push-pull broadcasts over one table, one seed and one
+        trial in one pass (gs_create_rumorset): cfg.model must be
+        "pushpull", trials 1 and pp_rounds "auto".  begin_rumors(senders) or
+        broadcast_begin(s) starts them; step / run / totals count the set
+        (received = (node, rumor) pairs, pending = started rumors below 99 %),
+        received() gives the nodes that hold every started rumor, and
+        rumor_results(), rumor_words() and rumor_column(j) the rumors themselves."""
+        return cls(cfg, _rumors=rumors)
 
     @classmethod
     def rank(cls, cfg: Config, nranks: int, rank: int, comm_id: bytes | None):
@@ -352,6 +367,36 @@ class Simulator:
         st = np.zeros(self.n * self.trials, dtype=np.uint8)
         self._check(self.L.gs_read_median_state(self.h, st.ctypes.data, st.size), "gs_read_median_state")
         return st if self.trials == 1 else st.reshape(self.trials, self.n)
+
+    def begin_rumors(self, senders):
+        """Rumor set: rumor j starts at senders[j] (len(senders) == rumors); a
+        negative entry draws that rumor's keyed sender (gs_rumorset_begin)."""
+        s = (C.c_int64 * len(senders))(*[int(x) for x in senders])
+        self._check(self.L.gs_rumorset_begin(self.h, s, len(senders)), "gs_rumorset_begin")
+
+    def rumor_results(self) -> list:
+        """Rumor set: per rumor a dict of sender, received (nodes that hold it),
+        tick_99 (first poll at which its float32 rule held, else 0) and started
+        (False: its sender was failed) (gs_rumorset_results)."""
+        buf = (_lib.RumorStats * max(1, self.rumors))()
+        k = C.c_size_t(0)
+        self._check(self.L.gs_rumorset_results(self.h, buf, self.rumors, C.byref(k)), "gs_rumorset_results")
+        return [dict(sender=int(buf[i].sender), received=int(buf[i].received), tick_99=int(buf[i].tick_99),
+                     started=bool(buf[i].started)) for i in range(k.value)]
+
+    def rumor_words(self) -> np.ndarray:
+        """Rumor set: [n] uint64, bit j of word v says that v holds rumor j
+        (gs_read_rumorset)."""
+        w = np.zeros(self.n, dtype=np.uint64)
+        self._check(self.L.gs_read_rumorset(self.h, w.ctypes.data, w.size), "gs_read_rumorset")
+        return w
+
+    def rumor_column(self, j: int) -> np.ndarray:
+        """Rumor set: the nodes that hold rumor j, ceil(n/64) words
+        (gs_read_rumor_column)."""
+        w = np.zeros(self.words, dtype=np.uint64)
+        self._check(self.L.gs_read_rumor_column(self.h, int(j), w.ctypes.data, w.size), "gs_read_rumor_column")
+        return w
 
     def trial_results(self) -> np.ndarray:
         """[trials, len(TRIAL_FIELDS)] int64: per trial its number, first

@@ -377,6 +377,57 @@ int gs_create_batch(const gs_params* params, gs_ctx** out);
  * device cannot be asked. */
 int gs_median_trials_max_n(int device, uint64_t* n_max);
 
+/* ---- concurrent rumors for push-pull ----
+ * Who calls whom in a push-pull round, and which calls are lost, does not
+ * depend on who is informed, so `rumors` broadcasts over one table with one
+ * seed share every table read and every draw.  A rumor set runs them in one
+ * pass: a uint64 per node whose bit j says that the node holds rumor j, and on
+ * every kept call to a live friend both ends learn everything the other held
+ * at the start of the round.  Column j of the words after round t is bit for
+ * bit the informed set of a one-rumor GS_MODEL_PUSHPULL context with the same
+ * seed, trial, table and mask after round t from sender j.  The counters are
+ * the set's own: fired counts every caller, sent every kept call, messages the
+ * ends of a connection that hold a rumor; received is the number of (node,
+ * rumor) pairs and pending the started rumors still below 99 %.
+ * gs_create_rumorset needs params.model == GS_MODEL_PUSHPULL, rumors in
+ * 1..GS_RUMORSET_MAX, trials <= 1 and no flag besides GS_FLAG_TIMING; anything
+ * else answers GS_EINVAL before any device call, the reason in
+ * gs_last_error(NULL).  crash_rate, delay_*, rumor_k and rumor_mode are
+ * unused.  One device.  The context takes gs_load_peers[_device],
+ * gs_build_overlay, gs_read_peers, gs_set_failed, gs_set_trial, gs_set_stream,
+ * gs_reset, gs_step, gs_run, gs_totals, gs_timing_get (deliver = the round,
+ * resolve = commit + publish) and gs_read_crashed like a one-trial push-pull
+ * context.  gs_broadcast_begin(ctx, s): s < 0 draws every sender, s >= 0
+ * starts rumor j at (s + j) mod n.  gs_run stops at the first poll at which
+ * every started rumor satisfies the float32 rule (GS_RUN_COVERED; if no rumor
+ * started, GS_RUN_QUIESCENT at the first poll), else at max_ticks: there is no
+ * test for "nothing can change any more".  gs_read_received gives the nodes
+ * that hold every started rumor; gs_trial_results one row for the set, its
+ * tick_99 the first poll with pending == 0; gs_read_removed and
+ * gs_read_median_state answer GS_EINVAL. */
+#define GS_RUMORSET_MAX 64u
+typedef struct gs_rumor_stats {
+  int64_t  sender;    /* the node the rumor started at                        */
+  uint64_t received;  /* nodes that hold it now                               */
+  uint64_t tick_99;   /* first poll at which the float32 rule held, else 0    */
+  int32_t  started;   /* 0: its sender was failed                             */
+  int32_t  reserved_;
+} gs_rumor_stats;
+int gs_create_rumorset(const gs_params* params, uint32_t rumors, gs_ctx** out);
+/* Rumor j starts at senders[j] (count must equal the set's rumors; an entry
+ * >= n: GS_EINVAL); a negative entry draws uniform(Philox{j, 0, 0, SENDER}, n),
+ * so rumor 0's keyed sender is the one gs_broadcast_begin(ctx, -1) draws on any
+ * context.  A rumor whose sender is failed does not start.  Two rumors may
+ * share a sender. */
+int gs_rumorset_begin(gs_ctx* ctx, const int64_t* senders, size_t count);
+/* One entry per rumor, in order (cap entries; *nout gets the count). */
+int gs_rumorset_results(gs_ctx* ctx, gs_rumor_stats* out, size_t cap, size_t* nout);
+/* The rumor words, have[n]: bit j of have[v] says that v holds rumor j. */
+int gs_read_rumorset(gs_ctx* ctx, uint64_t* have, size_t n);
+/* Column `rumor` of the words as a bitset, words[ceil(n/64)]: the informed set
+ * of that one broadcast. */
+int gs_read_rumor_column(gs_ctx* ctx, uint32_t rumor, uint64_t* words, size_t nwords);
+
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
  * Host buffers; copied.  Batched trials: trials tables back to back
