@@ -150,34 +150,63 @@ const char* gs_last_error(const gs_ctx* c) {
 // The limit queries have no context either: a HIP failure is reported like a
 // failed create's reason, through gs_last_error(NULL) and on stderr, with the
 // call that failed and the runtime's error.
-static int pp_trials_limit(int device, bool masked, uint64_t* n_max) {
+// `refuse` (not empty): an argument the query rejects before it looks at the
+// device.  limit(&lim): the engine's *_limit_error; max_n(lim): its plan's.
+static int trials_max_n(const char* name, int device, uint64_t* n_max, const std::string& refuse,
+                        const std::function<std::string(uint64_t*)>& limit,
+                        const std::function<uint64_t(uint64_t)>& max_n) {
   g_create_err.clear();
   if (!n_max) return GS_EINVAL;
   *n_max = 0;
   int ndev = 0;
+  int rc = GS_EDEVICE;
   std::string why;
   const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess) {
+  if (!refuse.empty()) {
+    why = refuse;
+    rc = GS_EINVAL;
+  } else if (ce != hipSuccess) {
     why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
   } else if (device < 0 || device >= ndev) {
     why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
   } else {
     uint64_t lim = 0;
-    why = ppt_limit_error(device, masked, &lim);
+    why = limit(&lim);
     if (why.empty()) {
-      *n_max = masked ? ppt_max_n_masked(lim) : ppt_max_n(lim);
+      *n_max = max_n(lim);
       return GS_OK;
     }
   }
   (void)hipGetLastError();
-  fprintf(stderr, "%s: %s\n", masked ? "gs_pp_trials_max_n_masked" : "gs_pp_trials_max_n", why.c_str());
+  fprintf(stderr, "%s: %s\n", name, why.c_str());
   g_create_err = why;
-  return GS_EDEVICE;
+  return rc;
 }
 
-int gs_pp_trials_max_n(int device, uint64_t* n_max) { return pp_trials_limit(device, false, n_max); }
+int gs_pp_trials_max_n(int device, uint64_t* n_max) {
+  return trials_max_n("gs_pp_trials_max_n", device, n_max, "",
+                      [&](uint64_t* lim) { return ppt_limit_error(device, false, lim); }, ppt_max_n);
+}
 
-int gs_pp_trials_max_n_masked(int device, uint64_t* n_max) { return pp_trials_limit(device, true, n_max); }
+int gs_pp_trials_max_n_masked(int device, uint64_t* n_max) {
+  return trials_max_n("gs_pp_trials_max_n_masked", device, n_max, "",
+                      [&](uint64_t* lim) { return ppt_limit_error(device, true, lim); }, ppt_max_n_masked);
+}
+
+int gs_median_trials_max_n(int device, uint64_t* n_max) {
+  return trials_max_n("gs_median_trials_max_n", device, n_max, "",
+                      [&](uint64_t* lim) { return mdt_limit_error(device, lim); }, mdt_max_n);
+}
+
+int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max) {
+  std::string refuse;
+  if (rumor_mode & ~(GS_RUMOR_BLIND | GS_RUMOR_COIN | GS_RUMOR_PULL))
+    refuse = "rumor_mode " + std::to_string(rumor_mode) + " has a bit that is none of GS_RUMOR_BLIND, GS_RUMOR_COIN, "
+             "GS_RUMOR_PULL";
+  return trials_max_n("gs_rumor_trials_max_n", device, n_max, refuse,
+                      [&](uint64_t* lim) { return rmt_limit_error(device, rumor_mode, lim); },
+                      [&](uint64_t lim) { return rmt_max_n(rumor_mode, lim); });
+}
 
 int gs_create(const gs_params* params, gs_ctx** out) {
   g_create_err.clear();
@@ -241,61 +270,6 @@ int gs_read_rumorset(gs_ctx* c, uint64_t* have, size_t n) {
 int gs_read_rumor_column(gs_ctx* c, uint32_t rumor, uint64_t* words, size_t nwords) {
   if (!c) return GS_EINVAL;
   return rs_read_column(c, rumor, words, nwords);
-}
-
-int gs_median_trials_max_n(int device, uint64_t* n_max) {
-  g_create_err.clear();
-  if (!n_max) return GS_EINVAL;
-  *n_max = 0;
-  int ndev = 0;
-  std::string why;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess) {
-    why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
-  } else if (device < 0 || device >= ndev) {
-    why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
-  } else {
-    uint64_t lim = 0;
-    why = mdt_limit_error(device, &lim);
-    if (why.empty()) {
-      *n_max = mdt_max_n(lim);
-      return GS_OK;
-    }
-  }
-  (void)hipGetLastError();
-  fprintf(stderr, "gs_median_trials_max_n: %s\n", why.c_str());
-  g_create_err = why;
-  return GS_EDEVICE;
-}
-
-int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max) {
-  g_create_err.clear();
-  if (!n_max) return GS_EINVAL;
-  *n_max = 0;
-  int ndev = 0;
-  int rc = GS_EDEVICE;
-  std::string why;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (rumor_mode & ~(GS_RUMOR_BLIND | GS_RUMOR_COIN | GS_RUMOR_PULL)) {
-    why = "rumor_mode " + std::to_string(rumor_mode) + " has a bit that is none of GS_RUMOR_BLIND, GS_RUMOR_COIN, "
-          "GS_RUMOR_PULL";
-    rc = GS_EINVAL;
-  } else if (ce != hipSuccess) {
-    why = std::string("hipGetDeviceCount: ") + hipGetErrorString(ce);
-  } else if (device < 0 || device >= ndev) {
-    why = "device " + std::to_string(device) + " of " + std::to_string(ndev) + " visible";
-  } else {
-    uint64_t lim = 0;
-    why = rmt_limit_error(device, rumor_mode, &lim);
-    if (why.empty()) {
-      *n_max = rmt_max_n(rumor_mode, lim);
-      return GS_OK;
-    }
-  }
-  (void)hipGetLastError();
-  fprintf(stderr, "gs_rumor_trials_max_n: %s\n", why.c_str());
-  g_create_err = why;
-  return rc;
 }
 
 int gs_create_multi(const gs_params* params, const int* devices, int ndev, gs_ctx** out) {

@@ -702,9 +702,7 @@ void account_members(gs_ctx* acc, const std::vector<gs_ctx*>& ms, uint64_t t0, u
 std::string ppt_limit_error(int device, bool masked, uint64_t* lim) {
   const char* where = "";
   const hipError_t e = ppt_lds_limit(device, masked, lim, &where);
-  if (e == hipSuccess) return std::string();
-  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
-         std::to_string((int)e) + ")";
+  return trial_limit_error(where, device, e);
 }
 
 // A batched push-pull context about to take failure masks: the masked LDS

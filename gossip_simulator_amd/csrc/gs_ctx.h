@@ -2,8 +2,9 @@
 // the error macros and the few host functions that cross the engine files
 // (gs_ctx.cpp lifetime, gs_peers.cpp tables, gs_windows.cpp / gs_shards.cpp
 // the flood engines, gs_pushpull_host.cpp push-pull, gs_rumor_host.cpp rumor
-// mongering, gs_median_host.cpp median-counter push-pull, gs_rumorset_host.cpp
-// concurrent push-pull rumors, gs_api.cpp the entry points).
+// mongering, gs_median_host.cpp median-counter push-pull, gs_trials_host.cpp
+// the batched trials' shared loops, gs_rumorset_host.cpp concurrent push-pull
+// rumors, gs_api.cpp the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,7 +111,6 @@ struct PpSparseBufs {
 // rumor_alloc / release_rumor
 struct RumorBufs {
   Buf list[2], hot, served, vain, miss, ctlb, removed, tri;
-  std::vector<uint32_t> hotn;  // batched: every trial's hot nodes after the last round run
   uint32_t cur = 0;   // list[cur] is the next round's read list
   uint32_t grid = 0;  // the round kernel's persistent grid (rumor_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
@@ -123,7 +123,6 @@ struct RumorBufs {
 // padded id space and the done bitset only: median_alloc / release_median
 struct MedianBufs {
   Buf st, own, tally, gotb, gotc, ctlb, done;
-  std::vector<uint32_t> actn;  // batched: every trial's active nodes after the last round run
   uint32_t grid = 0;  // the round kernel's persistent grid (median_begin)
   RumorCtl* h_ctl = nullptr;  // pinned copy of the control block, read once per poll
 };
@@ -143,12 +142,14 @@ struct RsBufs {
   uint64_t live = 0;                    // bit j: rumor j started
 };
 
-// batched trials' per-trial counter rows (both models) and the push-pull
+// batched trials' per-trial counter rows (every model) and the push-pull
 // trials' stall check: alloc_trial_rows / release_trials
 struct TrialRows {
   uint32_t* d_tstat = nullptr;          // [trials][kMaxWindow][kTStatFields]
   uint32_t* h_tstat = nullptr;          // pinned copy
   Buf chk;                              // the stall check's need bytes [trials] (4-aligned), then live u32 [trials]
+  // rumor and median trials: every trial's live (hot, active) nodes after the last round run (rumor_alloc, median_alloc)
+  std::vector<uint32_t> live;
 };
 
 // shard or rank exchange: finish_rank / release_exchange
@@ -441,6 +442,16 @@ int ppt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out);
 int ppt_poll_stops(gs_ctx* c, const std::vector<uint64_t>& r0, uint64_t max_ticks, uint32_t* running);
 void snap_trial(gs_ctx* c, uint32_t tr, int32_t status);
 bool trials_stopped(const gs_ctx* c, uint32_t running, int32_t* st);
+
+// gs_trials_host.cpp
+std::string trial_limit_error(const char* where, int device, hipError_t e);
+int trial_device_check(int device, std::string& why);
+using TrialLaunch = std::function<int(uint64_t t0, uint32_t batch)>;  // the rounds kernel, `batch` rounds from t0
+int trial_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls, const TrialLaunch& launch,
+               uint64_t (*row_msgs)(const uint32_t* r));
+int trial_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+              int32_t* status, const TrialLaunch& launch, uint64_t (*row_msgs)(const uint32_t* r));
+int trial_read_words(gs_ctx* c, uint64_t* words, const unsigned long long* d);
 
 // gs_rumor_host.cpp
 int rumor_refuse(const gs_params* params, const char* what);

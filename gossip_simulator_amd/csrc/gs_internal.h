@@ -485,6 +485,19 @@ hipError_t pp_count(const unsigned long long* words, uint64_t nwords, unsigned l
 hipError_t pp_or_slices(unsigned long long* dst, const unsigned long long* src, uint32_t nslices, uint64_t words,
                         hipStream_t st);
 
+// The trial-resident kernels' launch plumbing (gs_trials_host.cpp; DESIGN.md
+// section 4.10), one copy for the three engines below.
+// Per-workgroup LDS `device` grants `kernel` (a rounds kernel with a
+// kTrialMaxBlock launch bound), in bytes: the reported per-workgroup LDS,
+// confirmed by asking the runtime whether a full block with that much dynamic
+// LDS can be resident; if it cannot, the 64 KiB every HIP kernel may use
+// without opting in.  On an error *where (may be null) names the HIP call that
+// failed.
+hipError_t trial_lds_limit(int device, const void* kernel, uint64_t* limit, const char** where);
+// Past the default 64 KiB of dynamic LDS a kernel opts in, per device and per
+// instantiation: `count` of them to `bytes`.
+hipError_t trial_raise_lds(int device, const void* const* kernels, uint32_t count, uint32_t bytes);
+
 // Batched push-pull trials (gs_pushpull_trials.hip): one workgroup per trial,
 // the trial's informed set in LDS (plan: gs_ppt_plan.h), up to kMaxWindow
 // rounds per launch.  Nodes at trial << tlog | v as in every batched context.

@@ -12,20 +12,21 @@
 //                       largest block
 //   st       u8[64 W]   the state bytes every decision of the round reads (a
 //                       lane owns its node's byte)
-// 336 B per word and 320 B of scratch.  A trial fits when that is within what
-// the device grants one workgroup.  A failure mask is read from global
-// memory: it is no part of the plan.
+// 336 B per word and 320 B of scratch.  Block rule, fit and limit:
+// gs_trial_plan.h.  A failure mask is read from global memory: it is no part
+// of the plan.
 #ifndef GS_MDT_PLAN_H
 #define GS_MDT_PLAN_H
 
 #include <cstdint>
+#include "gs_trial_plan.h"
 
 namespace gs {
 
-constexpr uint32_t kMdtMaxBlock = 1024;  // threads: 16 waves
-constexpr uint32_t kMdtCounters = 5;     // fired, sent, messages, newly informed, active
-constexpr uint64_t kMdtScratchBytes = kMdtCounters * (kMdtMaxBlock / 64) * 4;  // 320 B
-constexpr uint64_t kMdtWordBytes = 64 * 4 + 8 + 8 + 64;                        // 336 B per 64 nodes
+constexpr uint32_t kMdtMaxBlock = kTrialMaxBlock;
+constexpr uint32_t kMdtCounters = 5;  // fired, sent, messages, newly informed, active
+constexpr uint64_t kMdtScratchBytes = trial_scratch_bytes(kMdtCounters);  // 320 B
+constexpr uint64_t kMdtWordBytes = 64 * 4 + 8 + 8 + 64;                   // 336 B per 64 nodes
 
 struct MdtPlan {
   uint64_t words = 0;  // ceil(n / 64)
@@ -36,8 +37,6 @@ struct MdtPlan {
   bool fits = false;       // lds_bytes <= the limit
 };
 
-// The block rule is push-pull's (gs_ppt_plan.h): the smallest of 64 .. 1024
-// threads (powers of two) that leaves a lane at most 16 nodes per round.
 inline MdtPlan mdt_plan(uint64_t n, uint64_t lds_limit_bytes) {
   MdtPlan p;
   p.words = (n + 63) / 64;
@@ -47,16 +46,13 @@ inline MdtPlan mdt_plan(uint64_t n, uint64_t lds_limit_bytes) {
   p.off_scratch = p.off_gotc + 8 * p.words;
   p.off_st = p.off_scratch + kMdtScratchBytes;
   p.lds_bytes = p.off_st + 64 * p.words;
-  p.block = 64;
-  while (p.block < kMdtMaxBlock && (uint64_t)p.block * 16 < n) p.block *= 2;
-  p.fits = n >= 1 && p.lds_bytes <= lds_limit_bytes;
+  p.block = trial_block(n);
+  p.fits = trial_fits(n, p.lds_bytes, lds_limit_bytes);
   return p;
 }
 
-// The largest n that fits (0: not even one word does).
 inline uint64_t mdt_max_n(uint64_t lds_limit_bytes) {
-  if (lds_limit_bytes < kMdtScratchBytes + kMdtWordBytes) return 0;
-  return (lds_limit_bytes - kMdtScratchBytes) / kMdtWordBytes * 64;
+  return trial_max_n(lds_limit_bytes, kMdtScratchBytes, kMdtWordBytes);
 }
 
 }  // namespace gs

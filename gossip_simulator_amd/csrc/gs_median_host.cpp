@@ -65,101 +65,24 @@ int mdt_begin(gs_ctx* c, uint64_t sender) {
   CK(c, hipStreamSynchronize(c->stream));
   c->recv = c->pending = 0;
   for (uint32_t tr = 0; tr < T; ++tr) {
-    c->md.actn[tr] = c->bt.h_tstat[tr];
+    c->bt.live[tr] = c->bt.h_tstat[tr];
     c->tacc[tr].start = c->tacc[tr].recv = c->bt.h_tstat[tr];
     c->recv += c->tacc[tr].recv;
-    c->pending += c->md.actn[tr];
+    c->pending += c->bt.live[tr];
   }
   c->begun = true;
   return GS_OK;
 }
 
-// `ticks` rounds of every trial, at most kMaxWindow per launch (rmt_step's
-// loop); out[k] = the sum of the trials' rows, pending = their active nodes.
-// tick_99 is taken at polls only (median_account's rule).
-int mdt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
-  CK(c, hipSetDevice(c->dev));
-  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
-  const MdtState ms = mdt_state(c);
-  const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
-  while (timing && c->ev.size() < 2) {
-    hipEvent_t ev;
-    CK(c, hipEventCreate(&ev));
-    c->ev.push_back(ev);
-  }
-  uint32_t done = 0;
-  while (done < ticks) {
-    const uint32_t batch = std::min<uint32_t>(ticks - done, kMaxWindow);
-    const uint64_t t0 = c->t + 1;
-    if (timing) CK(c, hipEventRecord(c->ev[0], c->stream));
+// The batch's rounds on the shared loops (gs_trials_host.cpp): the launcher,
+// and a row's messages = the active ends of the round's connections.
+TrialLaunch mdt_launch(gs_ctx* c) {
+  return [c, ms = mdt_state(c)](uint64_t t0, uint32_t batch) -> int {
     CK(c, mdt_rounds(ms, (uint32_t)t0, batch, c->stream));
-    if (timing) CK(c, hipEventRecord(c->ev[1], c->stream));
-    CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, tb, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    if (timing) {
-      float ms_ = 0;
-      CK(c, hipEventElapsedTime(&ms_, c->ev[0], c->ev[1]));
-      c->timing.deliver_ms += ms_;  // the rounds kernel: `batch` rounds of every trial
-      c->timing.deliver_launches++;
-    }
-    for (uint32_t k = 0; k < batch; ++k) {
-      const bool poll = every_tick_polls || done + k + 1 == ticks;
-      unsigned long long fired = 0, sent = 0, msgs = 0, act = 0;
-      for (uint32_t tr = 0; tr < c->trials; ++tr) {
-        const uint32_t* r = c->bt.h_tstat + ((size_t)tr * kMaxWindow + k) * kTStatFields;
-        TrialAcc& a = c->tacc[tr];
-        a.fired += r[TS_FIRED];
-        a.sent += r[TS_SENT];
-        a.msgs += r[TS_MSGS];
-        a.recv += r[TS_RECV];
-        if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = t0 + k;
-        c->md.actn[tr] = r[TS_HOT];
-        fired += r[TS_FIRED];
-        sent += r[TS_SENT];
-        msgs += r[TS_MSGS];
-        c->recv += r[TS_RECV];
-        act += r[TS_HOT];
-      }
-      c->t = t0 + k;
-      c->fired += fired;
-      c->sent += sent;
-      c->msgs += msgs;
-      c->pending = act;
-      if (out) out[done + k] = gs_tick_stats{c->t, fired, sent, msgs, c->recv, 0, c->pending};
-    }
-    done += batch;
-  }
-  return GS_OK;
+    return GS_OK;
+  };
 }
-
-// median_run's rule per trial: a trial stops at the first poll at which it has
-// no active node (covered or quiescent by the float32 rule at that poll), else
-// at max_ticks; the run ends when all have stopped.
-int mdt_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
-            int32_t* status) {
-  size_t k = 0;
-  int32_t st = GS_RUN_MAX_TICKS;
-  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
-  for (;;) {
-    RC(mdt_step(c, poll, nullptr, false));
-    if (out && k < cap)
-      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
-    ++k;
-    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
-    uint32_t running = 0;
-    for (uint32_t tr = 0; tr < c->trials; ++tr) {
-      TrialAcc& a = c->tacc[tr];
-      if (a.status != GS_RUN_RUNNING) continue;
-      if (c->md.actn[tr] == 0) snap_trial(c, tr, covered(a.recv, c->p.n) ? GS_RUN_COVERED : GS_RUN_QUIESCENT);
-      else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);
-      else ++running;
-    }
-    if (trials_stopped(c, running, &st)) break;
-  }
-  if (nout) *nout = k;
-  if (status) *status = st;
-  return GS_OK;
-}
+uint64_t mdt_row_msgs(const uint32_t* r) { return r[TS_MSGS]; }
 
 // The D set of every trial, built from the state bytes over the padded id
 // space (padding bytes are 0); trials x ceil(n/64) words, trial-major.
@@ -173,10 +96,7 @@ int mdt_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   m.st = (uint8_t*)c->md.st.p;
   if (c->begun) CK(c, median_done_set(c->st, m, d, c->stream));
   else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));  // (st is the last run's: nothing is informed)
-  CK(c, hipMemcpy2DAsync(words, Wn * 8, d, ((size_t)1 << c->tlog) / 8, Wn * 8, c->trials, hipMemcpyDeviceToHost,
-                         c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return GS_OK;
+  return trial_read_words(c, words, d);
 }
 
 // trials * n bytes, trial-major, without the padding of the internal layout.
@@ -196,13 +116,11 @@ int mdt_read_state(gs_ctx* c, uint8_t* st, size_t n) {
 
 }  // namespace
 
-// mdt_lds_limit with its failure in words ("" on success), as rmt_limit_error.
+// mdt_lds_limit with its failure in words ("" on success).
 std::string mdt_limit_error(int device, uint64_t* lim) {
   const char* where = "";
   const hipError_t e = mdt_lds_limit(device, lim, &where);
-  if (e == hipSuccess) return std::string();
-  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
-         std::to_string((int)e) + ")";
+  return trial_limit_error(where, device, e);
 }
 
 // Batched median trials (gs_create_batch): n is bounded by what `device`
@@ -213,16 +131,7 @@ std::string mdt_limit_error(int device, uint64_t* lim) {
 int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl) {
   *pl = MdtPlan{};
   if (p->trials <= 1 || p->model != GS_MODEL_MEDIAN) return GS_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    why = "no HIP device visible (libgossip_hip needs an MI355X)";
-    return GS_EDEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    why = "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)";
-    return GS_EDEVICE;
-  }
+  RC(trial_device_check(device, why));
   uint64_t lim = 0;
   why = mdt_limit_error(device, &lim);
   if (!why.empty()) {
@@ -285,7 +194,7 @@ int median_alloc(gs_ctx* c) {
   MedianBufs& b = c->md;
   if (c->mdt) {
     if (!grow(b.st, n)) return fail(c, GS_ENOMEM, "cannot allocate the batched median trials' state bytes");
-    b.actn.assign(c->trials, 0);
+    c->bt.live.assign(c->trials, 0);
     return GS_OK;
   }
   if (!grow(b.st, n) || !grow(b.own, n) || !grow(b.tally, n * 8) || !grow(b.gotb, c->st.W * 8) ||
@@ -331,7 +240,7 @@ int median_begin(gs_ctx* c, uint64_t sender) {
 // every_tick_polls: each tick is a poll (gs_step returns every tick's row);
 // else only the call's last tick is (gs_run).
 int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
-  if (c->mdt) return mdt_step(c, ticks, out, every_tick_polls);
+  if (c->mdt) return trial_step(c, ticks, out, every_tick_polls, mdt_launch(c), mdt_row_msgs);
   CK(c, hipSetDevice(c->dev));
   const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
   const MedianState ms = median_state(c);
@@ -387,7 +296,7 @@ int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_p
 int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
                int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
-  if (c->mdt) return mdt_run(c, poll, max_ticks, out, cap, nout, status);
+  if (c->mdt) return trial_run(c, poll, max_ticks, out, cap, nout, status, mdt_launch(c), mdt_row_msgs);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;

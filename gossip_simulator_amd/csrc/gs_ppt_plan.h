@@ -5,8 +5,7 @@
 // One workgroup runs one trial with the trial's informed set in LDS: two
 // bitsets (the round's `cur` and the `next` being built) of ceil(n / 64)
 // 8-byte words, then the block reduction's scratch (four u32 counters per
-// wave of the largest block).  A trial fits when that is within what the
-// device grants one workgroup.
+// wave of the largest block).  Block rule, fit and limit: gs_trial_plan.h.
 //
 // With per-trial failure masks (gs_set_failed on a batch) a third, read-only
 // bitset `F` of the trial's failed nodes sits beside them: three bitsets and
@@ -15,12 +14,13 @@
 #define GS_PPT_PLAN_H
 
 #include <cstdint>
+#include "gs_trial_plan.h"
 
 namespace gs {
 
-constexpr uint32_t kPptMaxBlock = 1024;                           // threads: 16 waves
-constexpr uint32_t kPptCounters = 4;                              // fired, sent, messages, received
-constexpr uint64_t kPptScratchBytes = kPptCounters * (kPptMaxBlock / 64) * 4;  // 256 B
+constexpr uint32_t kPptMaxBlock = kTrialMaxBlock;
+constexpr uint32_t kPptCounters = 4;                                        // fired, sent, messages, received
+constexpr uint64_t kPptScratchBytes = trial_scratch_bytes(kPptCounters);    // 256 B
 
 struct PptPlan {
   uint64_t words = 0;      // ceil(n / 64): words per bitset
@@ -29,37 +29,23 @@ struct PptPlan {
   bool fits = false;       // lds_bytes <= the limit
 };
 
-// Smaller blocks for small n: the smallest of 64 .. 1024 threads (powers of
-// two) that leaves a lane at most 16 nodes per round.
-inline PptPlan ppt_plan(uint64_t n, uint64_t lds_limit_bytes) {
+// `bitsets` bitsets (cur, next; masked: and F), then the scratch.
+inline PptPlan ppt_plan_of(uint64_t n, uint32_t bitsets, uint64_t lds_limit_bytes) {
   PptPlan p;
   p.words = (n + 63) / 64;
-  p.lds_bytes = 2 * p.words * 8 + kPptScratchBytes;
-  p.block = 64;
-  while (p.block < kPptMaxBlock && (uint64_t)p.block * 16 < n) p.block *= 2;
-  p.fits = n >= 1 && p.lds_bytes <= lds_limit_bytes;
+  p.lds_bytes = bitsets * p.words * 8 + kPptScratchBytes;
+  p.block = trial_block(n);
+  p.fits = trial_fits(n, p.lds_bytes, lds_limit_bytes);
   return p;
 }
 
-// The largest n that fits (0: not even one word does).
-inline uint64_t ppt_max_n(uint64_t lds_limit_bytes) {
-  if (lds_limit_bytes < kPptScratchBytes + 16) return 0;
-  return (lds_limit_bytes - kPptScratchBytes) / 16 * 64;
-}
+inline PptPlan ppt_plan(uint64_t n, uint64_t lds_limit_bytes) { return ppt_plan_of(n, 2, lds_limit_bytes); }
+inline uint64_t ppt_max_n(uint64_t lds_limit_bytes) { return trial_max_n(lds_limit_bytes, kPptScratchBytes, 2 * 8); }
 
-// The masked layout: cur, next and the failed set F, then the scratch.  Same
-// block rule.
-inline PptPlan ppt_plan_masked(uint64_t n, uint64_t lds_limit_bytes) {
-  PptPlan p = ppt_plan(n, lds_limit_bytes);
-  p.lds_bytes = 3 * p.words * 8 + kPptScratchBytes;
-  p.fits = n >= 1 && p.lds_bytes <= lds_limit_bytes;
-  return p;
-}
-
-// The largest n the masked layout fits (0: not even one word does).
+// The masked layout.
+inline PptPlan ppt_plan_masked(uint64_t n, uint64_t lds_limit_bytes) { return ppt_plan_of(n, 3, lds_limit_bytes); }
 inline uint64_t ppt_max_n_masked(uint64_t lds_limit_bytes) {
-  if (lds_limit_bytes < kPptScratchBytes + 24) return 0;
-  return (lds_limit_bytes - kPptScratchBytes) / 24 * 64;
+  return trial_max_n(lds_limit_bytes, kPptScratchBytes, 3 * 8);
 }
 
 }  // namespace gs

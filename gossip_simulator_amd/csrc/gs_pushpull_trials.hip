@@ -197,51 +197,17 @@ const void* rounds_kernel(bool masked) {
 
 }  // namespace
 
-// What the device grants one workgroup of k_ppt_rounds (either
-// instantiation): the reported per-workgroup LDS, confirmed by asking the
-// runtime whether a full block with that much dynamic LDS can be resident; if
-// it cannot, the 64 KiB every HIP kernel may use without opting in.
+// What the device grants one workgroup of that instantiation (trial_lds_limit,
+// gs_trials_host.cpp; the masked one has its own plan: F is in LDS).
 hipError_t ppt_lds_limit(int device, bool masked, uint64_t* limit, const char** where) {
-  int dev0 = 0, v = 0;
-  const char* dummy;
-  if (!where) where = &dummy;
-  *where = "hipGetDevice";
-  hipError_t e = hipGetDevice(&dev0);
-  if (e != hipSuccess) return e;
-  *where = "hipSetDevice";
-  if ((e = hipSetDevice(device)) != hipSuccess) return e;
-  *where = "hipDeviceGetAttribute(MaxSharedMemoryPerBlock)";
-  e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-  if (e == hipSuccess) {
-    uint64_t lim = v > 0 ? (uint64_t)v : 0;
-    if (lim > 65536) {
-      int nb = 0;
-      (void)hipFuncSetAttribute(rounds_kernel(masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim);
-      const hipError_t oe =
-          masked ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ppt_rounds<true>, (int)kPptMaxBlock, (size_t)lim)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ppt_rounds<false>, (int)kPptMaxBlock, (size_t)lim);
-      if (oe != hipSuccess || nb < 1) {
-        (void)hipGetLastError();
-        lim = 65536;
-      }
-    }
-    *limit = lim;
-  }
-  (void)hipSetDevice(dev0);
-  return e;
+  return trial_lds_limit(device, rounds_kernel(masked), limit, where);
 }
 
-// Past the default 64 KiB of dynamic LDS a kernel opts in, per device and per
-// instantiation: the unmasked one once per context, at create; the masked one
-// when the context gets its mask (raising the limit again is idempotent).
+// Per instantiation: the unmasked one once per context, at create; the masked
+// one when the context gets its mask (raising the limit again is idempotent).
 hipError_t ppt_prepare(int device, bool masked, uint32_t lds_bytes) {
-  int dev0 = 0;
-  hipError_t e = hipGetDevice(&dev0);
-  if (e != hipSuccess) return e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return e;
-  e = hipFuncSetAttribute(rounds_kernel(masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  (void)hipSetDevice(dev0);
-  return e;
+  const void* f = rounds_kernel(masked);
+  return trial_raise_lds(device, &f, 1, lds_bytes);
 }
 
 // s.crash set: the masked instantiation with the masked plan's LDS.

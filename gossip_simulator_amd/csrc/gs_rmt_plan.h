@@ -8,19 +8,20 @@
 // feedback also `served` and `vain` -- then the block reduction's scratch (five
 // u32 counters per wave of the largest block), then, unless GS_RUMOR_COIN, the
 // miss counts: one byte per node of the trial's words (64 per word, so a lane
-// owns its node's byte and the bytes of a word are the wave's own).  A trial
-// fits when that is within what the device grants one workgroup.  A failure
-// mask is read from global memory: it is no part of the plan.
+// owns its node's byte and the bytes of a word are the wave's own).  Block rule,
+// fit and limit: gs_trial_plan.h.  A failure mask is read from global memory:
+// it is no part of the plan.
 #ifndef GS_RMT_PLAN_H
 #define GS_RMT_PLAN_H
 
 #include <cstdint>
+#include "gs_trial_plan.h"
 
 namespace gs {
 
-constexpr uint32_t kRmtMaxBlock = 1024;  // threads: 16 waves
-constexpr uint32_t kRmtCounters = 5;     // fired, sent, messages, newly informed, hot
-constexpr uint64_t kRmtScratchBytes = kRmtCounters * (kRmtMaxBlock / 64) * 4;  // 320 B
+constexpr uint32_t kRmtMaxBlock = kTrialMaxBlock;
+constexpr uint32_t kRmtCounters = 5;  // fired, sent, messages, newly informed, hot
+constexpr uint64_t kRmtScratchBytes = trial_scratch_bytes(kRmtCounters);  // 320 B
 constexpr uint32_t kRmtBlind = 1, kRmtCoin = 2, kRmtPull = 4;  // gossip.h's GS_RUMOR_* bits
 
 struct RmtPlan {
@@ -37,24 +38,19 @@ inline bool rmt_has_miss(uint32_t mode) { return !(mode & kRmtCoin); }
 // LDS bytes per 64-node word of the trial.
 inline uint64_t rmt_word_bytes(uint32_t mode) { return rmt_bitsets(mode) * 8ull + (rmt_has_miss(mode) ? 64ull : 0ull); }
 
-// The block rule is push-pull's (gs_ppt_plan.h): the smallest of 64 .. 1024
-// threads (powers of two) that leaves a lane at most 16 nodes per round.
 inline RmtPlan rmt_plan(uint64_t n, uint32_t mode, uint64_t lds_limit_bytes) {
   RmtPlan p;
   p.words = (n + 63) / 64;
   p.bitsets = rmt_bitsets(mode);
   p.miss_bytes = rmt_has_miss(mode) ? 64 * p.words : 0;
   p.lds_bytes = p.bitsets * p.words * 8 + kRmtScratchBytes + p.miss_bytes;
-  p.block = 64;
-  while (p.block < kRmtMaxBlock && (uint64_t)p.block * 16 < n) p.block *= 2;
-  p.fits = n >= 1 && p.lds_bytes <= lds_limit_bytes;
+  p.block = trial_block(n);
+  p.fits = trial_fits(n, p.lds_bytes, lds_limit_bytes);
   return p;
 }
 
-// The largest n that fits (0: not even one word does).
 inline uint64_t rmt_max_n(uint32_t mode, uint64_t lds_limit_bytes) {
-  if (lds_limit_bytes < kRmtScratchBytes + rmt_word_bytes(mode)) return 0;
-  return (lds_limit_bytes - kRmtScratchBytes) / rmt_word_bytes(mode) * 64;
+  return trial_max_n(lds_limit_bytes, kRmtScratchBytes, rmt_word_bytes(mode));
 }
 
 }  // namespace gs

@@ -73,102 +73,24 @@ int rmt_begin(gs_ctx* c, uint64_t sender) {
   CK(c, hipStreamSynchronize(c->stream));
   c->recv = c->pending = 0;
   for (uint32_t tr = 0; tr < T; ++tr) {
-    c->rm.hotn[tr] = c->bt.h_tstat[tr];
+    c->bt.live[tr] = c->bt.h_tstat[tr];
     c->tacc[tr].start = c->tacc[tr].recv = c->bt.h_tstat[T + tr];
     c->recv += c->tacc[tr].recv;
-    c->pending += c->rm.hotn[tr];
+    c->pending += c->bt.live[tr];
   }
   c->begun = true;
   return GS_OK;
 }
 
-// `ticks` rounds of every trial, at most kMaxWindow per launch (ppt_step's
-// loop); out[k] = the sum of the trials' rows, pending = their hot nodes.
-// tick_99 is taken at polls only (rumor_account's rule): every tick, or only
-// the call's last.
-int rmt_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
-  CK(c, hipSetDevice(c->dev));
-  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
-  const RmtState rs = rmt_state(c);
-  const size_t tb = (size_t)c->trials * kMaxWindow * kTStatFields * 4;
-  while (timing && c->ev.size() < 2) {
-    hipEvent_t ev;
-    CK(c, hipEventCreate(&ev));
-    c->ev.push_back(ev);
-  }
-  uint32_t done = 0;
-  while (done < ticks) {
-    const uint32_t batch = std::min<uint32_t>(ticks - done, kMaxWindow);
-    const uint64_t t0 = c->t + 1;
-    if (timing) CK(c, hipEventRecord(c->ev[0], c->stream));
+// The batch's rounds on the shared loops (gs_trials_host.cpp): the launcher,
+// and a row's messages = the kept calls less those to a failed callee.
+TrialLaunch rmt_launch(gs_ctx* c) {
+  return [c, rs = rmt_state(c)](uint64_t t0, uint32_t batch) -> int {
     CK(c, rmt_rounds(rs, (uint32_t)t0, batch, c->stream));
-    if (timing) CK(c, hipEventRecord(c->ev[1], c->stream));
-    CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, tb, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    if (timing) {
-      float ms = 0;
-      CK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-      c->timing.deliver_ms += ms;  // the rounds kernel: `batch` rounds of every trial
-      c->timing.deliver_launches++;
-    }
-    for (uint32_t k = 0; k < batch; ++k) {
-      const bool poll = every_tick_polls || done + k + 1 == ticks;
-      unsigned long long fired = 0, sent = 0, msgs = 0, hot = 0;
-      for (uint32_t tr = 0; tr < c->trials; ++tr) {
-        const uint32_t* r = c->bt.h_tstat + ((size_t)tr * kMaxWindow + k) * kTStatFields;
-        TrialAcc& a = c->tacc[tr];
-        a.fired += r[TS_FIRED];
-        a.sent += r[TS_SENT];
-        a.msgs += (uint64_t)r[TS_SENT] - r[TS_DEAD];
-        a.recv += r[TS_RECV];
-        if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = t0 + k;
-        c->rm.hotn[tr] = r[TS_HOT];
-        fired += r[TS_FIRED];
-        sent += r[TS_SENT];
-        msgs += (uint64_t)r[TS_SENT] - r[TS_DEAD];
-        c->recv += r[TS_RECV];
-        hot += r[TS_HOT];
-      }
-      c->t = t0 + k;
-      c->fired += fired;
-      c->sent += sent;
-      c->msgs += msgs;
-      c->pending = hot;
-      if (out) out[done + k] = gs_tick_stats{c->t, fired, sent, msgs, c->recv, 0, c->pending};
-    }
-    done += batch;
-  }
-  return GS_OK;
+    return GS_OK;
+  };
 }
-
-// rumor_run's rule per trial: a trial stops at the first poll at which it has
-// no hot node (covered or quiescent by the float32 rule at that poll), else at
-// max_ticks; the run ends when all have stopped.
-int rmt_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
-            int32_t* status) {
-  size_t k = 0;
-  int32_t st = GS_RUN_MAX_TICKS;
-  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
-  for (;;) {
-    RC(rmt_step(c, poll, nullptr, false));
-    if (out && k < cap)
-      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
-    ++k;
-    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
-    uint32_t running = 0;
-    for (uint32_t tr = 0; tr < c->trials; ++tr) {
-      TrialAcc& a = c->tacc[tr];
-      if (a.status != GS_RUN_RUNNING) continue;
-      if (c->rm.hotn[tr] == 0) snap_trial(c, tr, covered(a.recv, c->p.n) ? GS_RUN_COVERED : GS_RUN_QUIESCENT);
-      else if (c->t >= max_ticks) snap_trial(c, tr, GS_RUN_MAX_TICKS);
-      else ++running;
-    }
-    if (trials_stopped(c, running, &st)) break;
-  }
-  if (nout) *nout = k;
-  if (status) *status = st;
-  return GS_OK;
-}
+uint64_t rmt_row_msgs(const uint32_t* r) { return (uint64_t)r[TS_SENT] - r[TS_DEAD]; }
 
 // removed = recv & ~hot in every mode of the batch; trials x ceil(n/64) words, trial-major.
 int rmt_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
@@ -181,21 +103,16 @@ int rmt_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   r.hot = (unsigned long long*)c->rm.hot.p;
   if (c->begun) CK(c, rumor_pull_removed(c->st, r, d, c->stream));
   else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));  // (hot is the last run's: nothing is informed)
-  CK(c, hipMemcpy2DAsync(words, Wn * 8, d, ((size_t)1 << c->tlog) / 8, Wn * 8, c->trials, hipMemcpyDeviceToHost,
-                         c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return GS_OK;
+  return trial_read_words(c, words, d);
 }
 
 }  // namespace
 
-// rmt_lds_limit with its failure in words ("" on success), as ppt_limit_error.
+// rmt_lds_limit with its failure in words ("" on success).
 std::string rmt_limit_error(int device, uint32_t mode, uint64_t* lim) {
   const char* where = "";
   const hipError_t e = rmt_lds_limit(device, mode, lim, &where);
-  if (e == hipSuccess) return std::string();
-  return std::string(where) + " on device " + std::to_string(device) + ": " + hipGetErrorString(e) + " (hipError_t " +
-         std::to_string((int)e) + ")";
+  return trial_limit_error(where, device, e);
 }
 
 // Batched rumor trials (gs_create_trials): n is bounded by what `device`
@@ -206,16 +123,7 @@ std::string rmt_limit_error(int device, uint32_t mode, uint64_t* lim) {
 int check_rmt_n(const gs_params* p, int device, std::string& why, RmtPlan* pl) {
   *pl = RmtPlan{};
   if (p->trials <= 1 || p->model != GS_MODEL_RUMOR) return GS_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    why = "no HIP device visible (libgossip_hip needs an MI355X)";
-    return GS_EDEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    why = "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)";
-    return GS_EDEVICE;
-  }
+  RC(trial_device_check(device, why));
   uint64_t lim = 0;
   why = rmt_limit_error(device, p->rumor_mode, &lim);
   if (!why.empty()) {
@@ -260,7 +168,7 @@ int rumor_alloc(gs_ctx* c) {
   if (c->rmt) {
     if (!grow(c->rm.hot, c->st.W * 8) || !grow(c->rm.miss, n) || !grow(c->rm.tri, (size_t)c->trials * 8))
       return fail(c, GS_ENOMEM, "cannot allocate the batched rumor trials' hot sets and miss counts");
-    c->rm.hotn.assign(c->trials, 0);
+    c->bt.live.assign(c->trials, 0);
     return GS_OK;
   }
   const bool sets = pull(c);
@@ -313,7 +221,7 @@ int rumor_begin(gs_ctx* c, uint64_t sender) {
 // every_tick_polls: each tick is a poll (gs_step returns every tick's row);
 // else only the call's last tick is (gs_run).
 int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
-  if (c->rmt) return rmt_step(c, ticks, out, every_tick_polls);
+  if (c->rmt) return trial_step(c, ticks, out, every_tick_polls, rmt_launch(c), rmt_row_msgs);
   CK(c, hipSetDevice(c->dev));
   const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
   const RumorState rs = rumor_state(c);
@@ -374,7 +282,7 @@ int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
 int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
               int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
-  if (c->rmt) return rmt_run(c, poll, max_ticks, out, cap, nout, status);
+  if (c->rmt) return trial_run(c, poll, max_ticks, out, cap, nout, status, rmt_launch(c), rmt_row_msgs);
   size_t k = 0;
   int32_t st = GS_RUN_MAX_TICKS;
   uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;

@@ -2,8 +2,11 @@
 // (GS_MODEL_RUMOR with trials > 1 through gs_create_trials; DESIGN.md section
 // 4.7.2, "trial-resident rounds").
 //
-// One workgroup runs one trial, on the pattern of k_ppt_rounds
-// (gs_pushpull_trials.hip).  The trial's state lives in LDS (plan:
+// One workgroup runs one trial, as in k_ppt_rounds (gs_pushpull_trials.hip).
+// The plan arithmetic, the launch plumbing and the host loops are shared with
+// it and with the median engine (gs_trial_plan.h, gs_trials_host.cpp); the
+// device code is this engine's own (DESIGN.md section 4.10 says why).  The
+// trial's state lives in LDS (plan:
 // gs_rmt_plan.h): the bitsets `cur` (the informed set every decision of the
 // round reads), `next` (the set being built) and `hot`, in feedback pull also
 // `served` and `vain`, and unless GS_RUMOR_COIN a miss byte per node.  A launch
@@ -345,51 +348,16 @@ const void* rounds_kernel(uint32_t mode, bool masked) {
 
 }  // namespace
 
-// What the device grants one workgroup of k_rmt_rounds, ppt_lds_limit's way:
-// the reported per-workgroup LDS, confirmed by asking the runtime whether a
-// full block of this mode's kernel with that much dynamic LDS can be resident;
-// if it cannot, the 64 KiB every HIP kernel may use without opting in.  (The
-// masked instantiation has the same plan: the mask is not in LDS.)
+// What the device grants one workgroup of this mode's kernel (trial_lds_limit,
+// gs_trials_host.cpp).  (The masked instantiation has the same plan: the mask
+// is not in LDS.)
 hipError_t rmt_lds_limit(int device, uint32_t mode, uint64_t* limit, const char** where) {
-  int dev0 = 0, v = 0;
-  const char* dummy;
-  if (!where) where = &dummy;
-  *where = "hipGetDevice";
-  hipError_t e = hipGetDevice(&dev0);
-  if (e != hipSuccess) return e;
-  *where = "hipSetDevice";
-  if ((e = hipSetDevice(device)) != hipSuccess) return e;
-  *where = "hipDeviceGetAttribute(MaxSharedMemoryPerBlock)";
-  e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-  if (e == hipSuccess) {
-    uint64_t lim = v > 0 ? (uint64_t)v : 0;
-    if (lim > 65536) {
-      int nb = 0;
-      const void* f = rounds_kernel(mode, false);
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim);
-      const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, (int)kRmtMaxBlock, (size_t)lim);
-      if (oe != hipSuccess || nb < 1) {
-        (void)hipGetLastError();
-        lim = 65536;
-      }
-    }
-    *limit = lim;
-  }
-  (void)hipSetDevice(dev0);
-  return e;
+  return trial_lds_limit(device, rounds_kernel(mode, false), limit, where);
 }
 
 hipError_t rmt_prepare(int device, uint32_t mode, uint32_t lds_bytes) {
-  int dev0 = 0;
-  hipError_t e = hipGetDevice(&dev0);
-  if (e != hipSuccess) return e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return e;
-  for (bool masked : {false, true}) {
-    e = hipFuncSetAttribute(rounds_kernel(mode, masked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) break;
-  }
-  (void)hipSetDevice(dev0);
-  return e;
+  const void* f[] = {rounds_kernel(mode, false), rounds_kernel(mode, true)};
+  return trial_raise_lds(device, f, 2, lds_bytes);
 }
 
 // s.crash set: the masked instantiation (the same LDS).

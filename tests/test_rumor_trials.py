@@ -104,7 +104,11 @@ def test_plan_header_on_the_host(tmp_path):
 
 
 def test_plan_header_includes_no_hip():
+    """No HIP header is reachable: <cstdint>, and the shared plan header, which includes <cstdint> only."""
     with open(os.path.join(CSRC, "gs_rmt_plan.h")) as f:
+        includes = re.findall(r"^#include\s+(\S+)", f.read(), re.M)
+    assert includes == ["<cstdint>", '"gs_trial_plan.h"']
+    with open(os.path.join(CSRC, "gs_trial_plan.h")) as f:
         includes = re.findall(r"^#include\s+(\S+)", f.read(), re.M)
     assert includes == ["<cstdint>"]
 
