@@ -17,6 +17,8 @@ Layers:
                             dense over bitsets (plan: gs_rmt_plan.h)
   csrc/gs_rumorset.hip      concurrent push-pull rumors (gs_create_rumorset): up to 64 broadcasts over
                             one table in one pass, a bit per rumor in a u64 per node; a dense engine
+  csrc/gs_rumorset_cap.hip  bounded rumor sets: the round under a payload cap per message, late starts
+                            (selection: gs_pick.h, plain C++ for host and device)
   csrc/gs_overlay.hip       overlay construction (makeup/breakup) on the GPU
   csrc/gs_api.cpp           C ABI entry points: argument checks, dispatch by context kind
   csrc/gs_ctx.h, gs_ctx.cpp the context behind the ABI: set-up and release of every kind

@@ -28,6 +28,7 @@ GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL = 1, 2, 4
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
 GS_COMM_ID_BYTES = 128
 GS_RUMORSET_MAX = 64
+GS_PICK_LOW, GS_PICK_HIGH, GS_PICK_ROTATE = 0, 1, 2
 
 # Every symbol include/gossip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -44,6 +45,7 @@ EXPORTS = (
     "gs_create_batch", "gs_median_trials_max_n",
     "gs_create_rumorset", "gs_rumorset_begin", "gs_rumorset_results", "gs_read_rumorset",
     "gs_read_rumor_column",
+    "gs_rumorset_set_payload", "gs_rumorset_begin_at", "gs_rumorset_traffic_get",
 )
 
 
@@ -91,6 +93,10 @@ class TrialStats(C.Structure):
 class RumorStats(C.Structure):
     _fields_ = [("sender", C.c_int64), ("received", C.c_uint64), ("tick_99", C.c_uint64),
                 ("started", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class RumorTraffic(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("wanted", "carried", "bound", "reserved_")]
 
 
 class Window(C.Structure):
@@ -187,6 +193,9 @@ def load():
         "gs_rumorset_results": ([ctx, P(RumorStats), sz, P(sz)], C.c_int),
         "gs_read_rumorset": ([ctx, vp, sz], C.c_int),
         "gs_read_rumor_column": ([ctx, C.c_uint32, vp, sz], C.c_int),
+        "gs_rumorset_set_payload": ([ctx, C.c_uint32, C.c_uint32], C.c_int),
+        "gs_rumorset_begin_at": ([ctx, P(C.c_int64), P(C.c_int64), sz], C.c_int),
+        "gs_rumorset_traffic_get": ([ctx, P(RumorTraffic)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

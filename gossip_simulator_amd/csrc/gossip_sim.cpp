@@ -4,11 +4,15 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -trials -device -peers -maxticks -model -k -batch -rumors) are not echoed in
+// (-seed -trial -trials -device -peers -maxticks -model -k -batch -rumors -payload -pick -every) are not echoed in
 // the parameter block, so stdout keeps the reference's shape.  -model pushpull
 // -rumors R runs R rumors from keyed senders as one rumor set
 // (gs_create_rumorset): each poll's line shows the least-covered started rumor,
-// then one line per rumor and the round at which all were covered.  -model rumor
+// then one line per rumor and the round at which all were covered; with
+// -payload B, -pick low|high|rotate or -every E the set is a bounded one
+// (DESIGN.md section 4.9.1): a message carries at most B rumors, rumor j enters
+// at round j * E, every rumor's line adds its start and its rounds from there to
+// 99 %, and a last line gives the rumor copies wanted and carried.  -model rumor
 // and -model median run to their own end and add the residue and the messages
 // per node (-model median: one trial, or -batch T trials through
 // gs_create_batch, printed like the rumor model's with a stranded column: the
@@ -193,24 +197,51 @@ bool load_peers_file(const std::string& path, uint64_t n, std::vector<uint8_t>& 
   return ok;
 }
 
+// -payload / -pick / -every of a -rumors run.
+struct BoundedSet {
+  bool on = false;       // one of the three flags was given
+  uint32_t payload = 0;  // rumors per message at most; 0: no cap
+  uint32_t pick = GS_PICK_LOW;
+  uint64_t every = 0;    // rumor j enters at round j * every
+};
+
 // -rumors R: R push-pull broadcasts from keyed senders in one pass (DESIGN.md
 // section 4.9).  One gs_run per 10-ms poll, so that every poll's line can show
 // the least-covered started rumor; then one line per rumor and the round at
-// which all were covered.
-int run_rumor_set(gs_ctx* c, const gs_params& p, uint32_t R, uint64_t max_ticks, double ov_wall) {
+// which all were covered.  A bounded set steps its ten rounds with gs_step
+// instead, under which every round is a poll: a rumor's round of 99 % is then
+// exact, as its rounds from start want it.  Without -payload it runs with a
+// payload of 64, which moves what no cap moves and counts the traffic.
+int run_rumor_set(gs_ctx* c, const gs_params& p, uint32_t R, uint64_t max_ticks, double ov_wall,
+                  const BoundedSet& bs) {
   printf("=== Broadcast %u rumors ===\n", R);
   fflush(stdout);
   const auto b0 = std::chrono::steady_clock::now();
-  int rc = gs_broadcast_begin(c, -1);  // every sender keyed
-  if (rc) return die(c, rc, "gs_broadcast_begin");
+  int rc;
+  if (bs.on) {
+    rc = gs_rumorset_set_payload(c, bs.payload ? bs.payload : GS_RUMORSET_MAX, bs.pick);
+    if (rc) return die(c, rc, "gs_rumorset_set_payload");
+    std::vector<int64_t> senders(R, -1), starts(R);
+    for (uint32_t j = 0; j < R; ++j) starts[j] = (int64_t)(j * bs.every);
+    rc = gs_rumorset_begin_at(c, senders.data(), starts.data(), R);
+    if (rc) return die(c, rc, "gs_rumorset_begin_at");
+  } else {
+    rc = gs_broadcast_begin(c, -1);  // every sender keyed
+    if (rc) return die(c, rc, "gs_broadcast_begin");
+  }
   std::vector<gs_rumor_stats> rs(R);
   size_t nrs = 0;
   int32_t status = GS_RUN_MAX_TICKS;
   gs_tick_stats tot{};
   do {
     gs_totals(c, &tot);
-    rc = gs_run(c, 10, std::min<uint64_t>(tot.tick + 10, max_ticks), nullptr, 0, nullptr, &status);  // one poll
-    if (rc) return die(c, rc, "gs_run");
+    if (bs.on) {
+      rc = gs_step(c, (uint32_t)std::min<uint64_t>(10, max_ticks - std::min(tot.tick, max_ticks)), nullptr);
+      if (rc) return die(c, rc, "gs_step");
+    } else {
+      rc = gs_run(c, 10, std::min<uint64_t>(tot.tick + 10, max_ticks), nullptr, 0, nullptr, &status);  // one poll
+      if (rc) return die(c, rc, "gs_run");
+    }
     rc = gs_rumorset_results(c, rs.data(), rs.size(), &nrs);
     if (rc) return die(c, rc, "gs_rumorset_results");
     gs_totals(c, &tot);
@@ -221,15 +252,25 @@ int run_rumor_set(gs_ctx* c, const gs_params& p, uint32_t R, uint64_t max_ticks,
         least = std::min<uint64_t>(least, rs[j].received);
         any = true;
       }
+    if (bs.on) status = !any ? GS_RUN_QUIESCENT : tot.pending == 0 ? GS_RUN_COVERED : GS_RUN_MAX_TICKS;  // gs_run's rule
     char pb[64];
     gs_format_float32((any ? (float)least / (float)p.n : 0.0f) * 100.0f, pb, sizeof(pb));
     printf("%s%% covered, took %s\n", pb, dur_ms(tot.tick).c_str());
   } while (status == GS_RUN_MAX_TICKS && tot.tick < max_ticks);
   for (uint32_t j = 0; j < R; ++j) {
     printf("rumor %u: sender %" PRId64 ", %" PRIu64 " nodes, ", j, rs[j].sender, rs[j].received);
+    if (bs.on) printf("start %s, ", dur_ms(j * bs.every).c_str());
     if (!rs[j].started) printf("never started (its sender is failed)\n");
+    else if (rs[j].tick_99 && bs.on)
+      printf("99%% after %s, %" PRIu64 " rounds from start\n", dur_ms(rs[j].tick_99).c_str(),
+             rs[j].tick_99 - j * bs.every);
     else if (rs[j].tick_99) printf("99%% after %s\n", dur_ms(rs[j].tick_99).c_str());
     else printf("99%% not reached\n");
+  }
+  gs_rumorset_traffic tr{};
+  if (bs.on) {
+    rc = gs_rumorset_traffic_get(c, &tr);
+    if (rc) return die(c, rc, "gs_rumorset_traffic_get");
   }
   const double bc_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count();
   if (status != GS_RUN_COVERED) {
@@ -241,6 +282,9 @@ int run_rumor_set(gs_ctx* c, const gs_params& p, uint32_t R, uint64_t max_ticks,
   }
   printf("--- Took %s to get 99%% of all %u rumors ---\n\n", dur_ms(tot.tick).c_str(), R);
   printf("Total message %" PRIu64 " Total Crashed %" PRIu64 "\n", tot.messages, tot.crashed);
+  if (bs.on)
+    printf("Rumor copies wanted %" PRIu64 " carried %" PRIu64 ", messages bound by the payload %" PRIu64 "\n", tr.wanted,
+           tr.carried, tr.bound);
   fflush(stdout);
   fprintf(stderr, "[gossip_sim] wall: overlay %.3f s, %u rumors %.3f s\n", ov_wall, R, bc_wall);
   gs_destroy(c);
@@ -284,6 +328,11 @@ int main(int argc, char** argv) {
        "false"},
       {"rumors", "int", "pushpull model: this many rumors, 1..64, from keyed senders over one table in one pass "
        "(gs_create_rumorset; one line per rumor)", "0", false, "0"},
+      {"payload", "int", "with -rumors: a message carries at most this many rumors, 1..64 (0: no cap; "
+       "gs_rumorset_set_payload)", "0", false, "0"},
+      {"pick", "string", "with -rumors: which wanted rumors a capped message carries: low (lowest indices, oldest "
+       "first), high or rotate", "low", false, "low"},
+      {"every", "int", "with -rumors: rumor j enters at round j * this (gs_rumorset_begin_at)", "0", false, "0"},
       {"maxticks", "int", "give up after this many simulated ms per phase", "10000000", false,
        "10000000"},
   };
@@ -350,6 +399,38 @@ int main(int argc, char** argv) {
     fprintf(stderr, "flag -rumors with -trials or -gpus above 1: a rumor set runs one trial on one device\n");
     usage();
     return 2;
+  }
+  BoundedSet bs;
+  for (const char* name : {"payload", "pick", "every"}) {
+    if (!find(name)->given) continue;
+    if (!rumor_set) {
+      fprintf(stderr, "flag -%s needs -rumors (it bounds a rumor set)\n", name);
+      usage();
+      return 2;
+    }
+    bs.on = true;
+  }
+  if (bs.on) {
+    const std::string pk = find("pick")->val;
+    if (ival("payload") < 0 || ival("payload") > (long long)GS_RUMORSET_MAX) {
+      fprintf(stderr, "invalid value \"%s\" for flag -payload: want 0..64\n", find("payload")->val.c_str());
+      usage();
+      return 2;
+    }
+    if (pk != "low" && pk != "high" && pk != "rotate") {
+      fprintf(stderr, "invalid value \"%s\" for flag -pick: want low, high or rotate\n", pk.c_str());
+      usage();
+      return 2;
+    }
+    if (ival("every") < 0 || ival("every") * (ival("rumors") - 1) > 0x7FFFFFFFll || ival("every") > 0x7FFFFFFFll) {
+      fprintf(stderr, "invalid value \"%s\" for flag -every: the last rumor's start must be a round below 2^31\n",
+              find("every")->val.c_str());
+      usage();
+      return 2;
+    }
+    bs.payload = (uint32_t)ival("payload");
+    bs.pick = pk == "high" ? GS_PICK_HIGH : pk == "rotate" ? GS_PICK_ROTATE : GS_PICK_LOW;
+    bs.every = (uint64_t)ival("every");
   }
 
   uint32_t rumor_mode = 0;
@@ -459,7 +540,7 @@ int main(int argc, char** argv) {
   printf("--- Took %s to stabilize ---\n\n", dur_ms(stab).c_str()); // :235
   const double ov_wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
 
-  if (rumor_set) return run_rumor_set(c, p, (uint32_t)ival("rumors"), max_ticks, ov_wall);
+  if (rumor_set) return run_rumor_set(c, p, (uint32_t)ival("rumors"), max_ticks, ov_wall, bs);
   printf("=== Broadcast one message ===\n");                    // :237
   fflush(stdout);
   const auto b0 = std::chrono::steady_clock::now();

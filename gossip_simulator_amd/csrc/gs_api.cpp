@@ -257,6 +257,33 @@ int gs_rumorset_begin(gs_ctx* c, const int64_t* senders, size_t count) {
   return rs_begin(c, senders);
 }
 
+int gs_rumorset_begin_at(gs_ctx* c, const int64_t* senders, const int64_t* starts, size_t count) {
+  if (!c) return GS_EINVAL;
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_rumorset_begin_at needs a gs_create_rumorset context");
+  if (!c->peers) return fail(c, GS_EINVAL, "load peers or build the overlay first");
+  if (c->begun) return fail(c, GS_EINVAL, "broadcast already begun");
+  if (!senders || count != c->rumors)
+    return fail(c, GS_EINVAL, "the set has " + std::to_string(c->rumors) + " rumors: count must equal it");
+  for (size_t j = 0; j < count; ++j) {
+    if (senders[j] >= 0 && (uint64_t)senders[j] >= c->p.n)
+      return fail(c, GS_EINVAL, "sender " + std::to_string(j) + " out of range");
+    if (starts && (starts[j] < 0 || starts[j] > 0x7FFFFFFFll))
+      return fail(c, GS_EINVAL, "start " + std::to_string(j) + " must be a round in 0..2^31-1");
+  }
+  reset_counters(c);
+  return rs_begin(c, senders, starts);
+}
+
+int gs_rumorset_set_payload(gs_ctx* c, uint32_t payload, uint32_t pick) {
+  if (!c) return GS_EINVAL;
+  return rs_set_payload(c, payload, pick);
+}
+
+int gs_rumorset_traffic_get(gs_ctx* c, gs_rumorset_traffic* out) {
+  if (!c) return GS_EINVAL;
+  return rs_traffic(c, out);
+}
+
 int gs_rumorset_results(gs_ctx* c, gs_rumor_stats* out, size_t cap, size_t* nout) {
   if (!c) return GS_EINVAL;
   return rs_results(c, out, cap, nout);

@@ -140,6 +140,11 @@ struct RsBufs {
   uint64_t count[kRsMax] = {};          // nodes that hold each rumor, as of the last row read
   uint64_t tick99[kRsMax] = {};         // first poll at which its float32 rule held, else 0
   uint64_t live = 0;                    // bit j: rumor j started
+  // bounded sets (section 4.9.1; gs_rumorset_cap.hip)
+  uint32_t payload = 0, pick = 0;       // rumors a message carries at most (0: no cap) and GS_PICK_*; outlive a reset
+  uint32_t start[kRsMax] = {};          // the round after whose commit rumor j enters (0: at begin)
+  uint32_t last_start = 0;              // the largest of them: no round after it injects
+  RsSenders snd = {};                   // the senders as the inject kernel takes them
 };
 
 // batched trials' per-trial counter rows (every model) and the push-pull
@@ -483,7 +488,9 @@ int mdt_load_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32_t st
 int rs_check_create(const gs_params* params, uint32_t rumors);
 int rs_alloc(gs_ctx* c);
 void release_rumorset(gs_ctx* c);
-int rs_begin(gs_ctx* c, const int64_t* senders);
+int rs_begin(gs_ctx* c, const int64_t* senders, const int64_t* starts = nullptr);  // starts NULL: every rumor at begin
+int rs_set_payload(gs_ctx* c, uint32_t payload, uint32_t pick);
+int rs_traffic(gs_ctx* c, gs_rumorset_traffic* out);
 int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls);
 int rs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
            int32_t* status);

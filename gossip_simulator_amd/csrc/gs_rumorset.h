@@ -13,9 +13,11 @@ constexpr uint32_t kRsMax = 64;  // GS_RUMORSET_MAX: a bit per rumor in a u64 pe
 // then the round's newly informed nodes per rumor; the rest is written by one
 // wave per round (k_rs_seed, k_rs_publish) and read by the next kernels.
 enum RsAcc : uint32_t { RS_FIRED = 0, RS_SENT = 1, RS_MSGS = 2 };
+enum RsTraffic : uint32_t { RS_WANTED = 0, RS_CARRIED = 1, RS_BOUND = 2 };
 struct RsCtl {
   unsigned long long acc[3];    // the round's fired / sent / messages (RsAcc)
-  unsigned long long pad0_[29];
+  unsigned long long traffic[3];  // the broadcast's wanted / carried / bound (RsTraffic; k_rsc_round, section 4.9.1)
+  unsigned long long pad0_[26];
   unsigned long long newc[kRsMax];  // the round's newly informed nodes per rumor (two blocks)
   unsigned long long cnt[kRsMax];   // nodes that hold rumor j, cumulative
   unsigned long long cover;     // smallest count the float32 coverage rule accepts
@@ -52,5 +54,15 @@ hipError_t rs_round(const DevState& s, const RsState& r, uint32_t t, uint32_t gr
 hipError_t rs_commit(const DevState& s, const RsState& r, uint32_t t, uint32_t grid, hipStream_t st);
 // out[W] = bit `rumor` of every word of have.
 hipError_t rs_column(const DevState& s, const RsState& r, uint32_t rumor, unsigned long long* out, hipStream_t st);
+
+// gs_rumorset_cap.hip: a payload cap per message and late starts.
+// rs_seed with starts: `now` has bit j where rumor j enters at begin; the others are live but not yet held by anyone.
+hipError_t rsc_seed(const DevState& s, const RsState& r, const RsSenders& snd, unsigned long long now,
+                    unsigned long long cover, hipStream_t st);
+// Between a round's kernel and its commit: the rumors of `mask` enter at their senders (bits of next).
+hipError_t rsc_inject(const RsState& r, const RsSenders& snd, unsigned long long mask, hipStream_t st);
+// rs_round under a cap of `payload` rumors (1..64) per message, `pick` one of GS_PICK_*; adds to ctl->traffic.
+hipError_t rsc_round(const DevState& s, const RsState& r, uint32_t t, uint32_t payload, uint32_t pick, uint32_t grid,
+                     hipStream_t st);
 
 }  // namespace gs

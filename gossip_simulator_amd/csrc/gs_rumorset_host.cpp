@@ -82,25 +82,33 @@ void release_rumorset(gs_ctx* c) {
 }
 
 // senders[j] < 0: rumor j's keyed sender.  A failed sender starts nothing; if
-// none starts the first poll is quiescent.
-int rs_begin(gs_ctx* c, const int64_t* senders) {
+// none starts the first poll is quiescent.  starts (section 4.9.1): rumor j
+// enters after round starts[j]'s commit; NULL, or every entry 0, is the begin
+// of section 4.9 with its own seed kernel.
+int rs_begin(gs_ctx* c, const int64_t* senders, const int64_t* starts) {
   CK(c, hipSetDevice(c->dev));
   // GS_RUMORSET_GRID: the blocks of the round and the commit (read per
   // broadcast, so tests can make a short table take several passes of the grid)
   const char* e = getenv("GS_RUMORSET_GRID");
   RsBufs& b = c->rsb;
   b.grid = rs_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
-  RsSenders snd{};
+  b.snd = RsSenders{};
+  b.last_start = 0;
+  unsigned long long now = 0;
   for (uint32_t j = 0; j < c->rumors; ++j) {
-    snd.node[j] = senders[j] >= 0 ? (uint32_t)senders[j]
-                                  : uniform(draw0(c->st.key, K_SENDER, j, 0, 0), (uint32_t)c->p.n);
-    b.sender[j] = snd.node[j];
+    b.snd.node[j] = senders[j] >= 0 ? (uint32_t)senders[j]
+                                    : uniform(draw0(c->st.key, K_SENDER, j, 0, 0), (uint32_t)c->p.n);
+    b.sender[j] = b.snd.node[j];
     b.tick99[j] = 0;
+    b.start[j] = starts ? (uint32_t)starts[j] : 0u;
+    b.last_start = std::max(b.last_start, b.start[j]);
+    if (b.start[j] == 0) now |= 1ull << j;
   }
   CK(c, hipMemsetAsync(b.ctlb.p, 0, sizeof(RsCtl), c->stream));
   for (Buf* q : {&b.have, &b.next, &b.own}) CK(c, hipMemsetAsync(q->p, 0, c->st.n * 8, c->stream));
   CK(c, hipMemsetAsync(c->st.recv, 0, c->st.W * 8, c->stream));
-  CK(c, rs_seed(c->st, rs_state(c), snd, cover_threshold(c->p.n), c->stream));
+  if (b.last_start == 0) CK(c, rs_seed(c->st, rs_state(c), b.snd, cover_threshold(c->p.n), c->stream));
+  else CK(c, rsc_seed(c->st, rs_state(c), b.snd, now, cover_threshold(c->p.n), c->stream));
   CK(c, hipMemcpyAsync(b.h_ctl, b.ctlb.p, sizeof(RsCtl), hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
   b.live = b.h_ctl->live;
@@ -111,8 +119,42 @@ int rs_begin(gs_ctx* c, const int64_t* senders) {
   return GS_OK;
 }
 
-// `ticks` rounds, three launches each, enqueued without a host sync between
-// them; the stats rows, the count ring's slots and the control block come back
+// The cap of the next broadcasts: refused while one is under way, so that a
+// broadcast's traffic counters belong to one cap; gs_reset and gs_set_trial keep it.
+int rs_set_payload(gs_ctx* c, uint32_t payload, uint32_t pick) {
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_rumorset_set_payload needs a gs_create_rumorset context");
+  if (payload > GS_RUMORSET_MAX)
+    return fail(c, GS_EINVAL, "payload must be 0 (no cap) or 1..64 rumors per message, not " + std::to_string(payload));
+  if (pick > GS_PICK_ROTATE)
+    return fail(c, GS_EINVAL, "pick must be GS_PICK_LOW, GS_PICK_HIGH or GS_PICK_ROTATE, not " + std::to_string(pick));
+  if (c->begun) return fail(c, GS_EINVAL, "gs_reset before gs_rumorset_set_payload (a broadcast is under way)");
+  c->rsb.payload = payload;
+  c->rsb.pick = pick;
+  return GS_OK;
+}
+
+// The counters are k_rsc_round's: an uncapped set (payload 0) runs k_rs_round,
+// which counts none of them, so it answers GS_EINVAL (payload 64 counts and
+// moves what no cap moves).  As of the last round a gs_step or gs_run read back.
+int rs_traffic(gs_ctx* c, gs_rumorset_traffic* out) {
+  if (!c->rset) return fail(c, GS_EINVAL, "gs_rumorset_traffic_get needs a gs_create_rumorset context");
+  if (!out) return fail(c, GS_EINVAL, "out is NULL");
+  const RsBufs& b = c->rsb;
+  if (b.payload == 0)
+    return fail(c, GS_EINVAL, "gs_rumorset_traffic_get: an uncapped set does not count its traffic "
+                              "(gs_rumorset_set_payload(ctx, 64, pick) moves the same and counts)");
+  *out = gs_rumorset_traffic{};
+  if (c->begun) {
+    out->wanted = b.h_ctl->traffic[RS_WANTED];
+    out->carried = b.h_ctl->traffic[RS_CARRIED];
+    out->bound = b.h_ctl->traffic[RS_BOUND];
+  }
+  return GS_OK;
+}
+
+// `ticks` rounds, three launches each (a capped set's round kernel is
+// gs_rumorset_cap.hip's; one more launch in a round after which a late rumor
+// enters), enqueued without a host sync between them; the stats rows, the count ring's slots and the control block come back
 // once per call (per kStatSlots rounds).  every_tick_polls: each tick is a
 // poll (gs_step); else only the call's last tick is (gs_run).
 int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
@@ -134,8 +176,15 @@ int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls
       const uint32_t tt = (uint32_t)(t0 + i);
       hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
       if (ev) CK(c, hipEventRecord(ev[0], c->stream));
-      CK(c, rs_round(c->st, rs, tt, b.grid, c->stream));
+      if (b.payload) CK(c, rsc_round(c->st, rs, tt, b.payload, b.pick, b.grid, c->stream));
+      else CK(c, rs_round(c->st, rs, tt, b.grid, c->stream));
       if (ev) CK(c, hipEventRecord(ev[1], c->stream));
+      if (tt <= b.last_start) {  // the live rumors that enter after this round's commit (the host knows the starts)
+        unsigned long long in = 0;
+        for (uint32_t j = 0; j < c->rumors; ++j)
+          if (b.start[j] == tt) in |= 1ull << j;
+        if (in & b.live) CK(c, rsc_inject(rs, b.snd, in & b.live, c->stream));
+      }
       CK(c, rs_commit(c->st, rs, tt, b.grid, c->stream));
       if (ev) CK(c, hipEventRecord(ev[2], c->stream));
     }

@@ -368,11 +368,38 @@ class Simulator:
         self._check(self.L.gs_read_median_state(self.h, st.ctypes.data, st.size), "gs_read_median_state")
         return st if self.trials == 1 else st.reshape(self.trials, self.n)
 
-    def begin_rumors(self, senders):
+    def begin_rumors(self, senders, starts=None):
         """Rumor set: rumor j starts at senders[j] (len(senders) == rumors); a
-        negative entry draws that rumor's keyed sender (gs_rumorset_begin)."""
+        negative entry draws that rumor's keyed sender (gs_rumorset_begin).
+        starts: rumor j enters after round starts[j]'s commit, 0 = at begin
+        (gs_rumorset_begin_at); None: every rumor at begin."""
         s = (C.c_int64 * len(senders))(*[int(x) for x in senders])
-        self._check(self.L.gs_rumorset_begin(self.h, s, len(senders)), "gs_rumorset_begin")
+        if starts is None:
+            self._check(self.L.gs_rumorset_begin(self.h, s, len(senders)), "gs_rumorset_begin")
+            return
+        if len(starts) != len(senders):
+            raise ValueError("starts must have one entry per sender")
+        a = (C.c_int64 * len(starts))(*[int(x) for x in starts])
+        self._check(self.L.gs_rumorset_begin_at(self.h, s, a, len(senders)), "gs_rumorset_begin_at")
+
+    PICKS = {"low": _lib.GS_PICK_LOW, "high": _lib.GS_PICK_HIGH, "rotate": _lib.GS_PICK_ROTATE}
+
+    def set_payload(self, B: int, pick="low"):
+        """Rumor set: a message carries at most B rumors (1..64; 0 = no cap),
+        chosen among the wanted ones by pick: "low" (lowest indices), "high" or
+        "rotate" (upwards from a keyed offset), or a GS_PICK_* value.  Before a
+        begin or after reset(); kept by reset() and set_trial()
+        (gs_rumorset_set_payload)."""
+        code = self.PICKS[pick] if isinstance(pick, str) else int(pick)
+        self._check(self.L.gs_rumorset_set_payload(self.h, int(B), code), "gs_rumorset_set_payload")
+
+    def rumor_traffic(self) -> dict:
+        """Capped rumor set: the rumor copies wanted and carried and the
+        messages the cap bound, cumulative over the broadcast
+        (gs_rumorset_traffic_get; an error on an uncapped set)."""
+        t = _lib.RumorTraffic()
+        self._check(self.L.gs_rumorset_traffic_get(self.h, C.byref(t)), "gs_rumorset_traffic_get")
+        return dict(wanted=int(t.wanted), carried=int(t.carried), bound=int(t.bound))
 
     def rumor_results(self) -> list:
         """Rumor set: per rumor a dict of sender, received (nodes that hold it),

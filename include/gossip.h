@@ -428,6 +428,51 @@ int gs_read_rumorset(gs_ctx* ctx, uint64_t* have, size_t n);
  * of that one broadcast. */
 int gs_read_rumor_column(gs_ctx* ctx, uint32_t rumor, uint64_t* words, size_t nwords);
 
+/* ---- bounded rumor sets ----
+ * A payload cap: a message carries at most `payload` rumors (1..64; 0 = no
+ * cap, the section 4.9 path).  The ends of a connection are taken to exchange
+ * digests, so with H the words at the start of the round and v the caller of
+ * u, the caller's message carries give = pick(H[v] & ~H[u], o_push) and the
+ * reply take = pick(H[u] & ~H[v], o_pull); next[u] |= give, next[v] |= take.
+ * The cap is per message: a node that several callers reach receives up to
+ * `payload` rumors from each.  pick(x, o) is x if it has at most `payload`
+ * bits, else its `payload` lowest set bits (GS_PICK_LOW: with starts in index
+ * order, oldest first), its highest (GS_PICK_HIGH: newest first) or the first
+ * `payload` met going up from index o, wrapping from R - 1 to 0
+ * (GS_PICK_ROTATE; o_push = uniform(r.z, R) and o_pull = uniform(r.w, R) of
+ * the draw r the caller already makes).  Rumors compete for the payload, so a
+ * column is no longer a one-rumor broadcast; fired, sent, messages, received
+ * and pending keep their meaning.  payload >= 1 always runs the capped round
+ * kernel, which moves what no cap moves once payload >= rumors.
+ * gs_rumorset_set_payload: rumor-set contexts only; payload > 64 or an unknown
+ * pick answers GS_EINVAL; refused between a begin and the next gs_reset; kept
+ * by gs_reset and gs_set_trial. */
+#define GS_PICK_LOW 0u
+#define GS_PICK_HIGH 1u
+#define GS_PICK_ROTATE 2u
+int gs_rumorset_set_payload(gs_ctx* ctx, uint32_t payload, uint32_t pick);
+/* gs_rumorset_begin with a start round per rumor, 0 <= starts[j] < 2^31
+ * (starts NULL: every rumor at begin, which gs_rumorset_begin and
+ * gs_broadcast_begin keep meaning).  Bit j is set at senders[j] after round
+ * starts[j]'s commit, so that round's row and per-rumor count include it
+ * (count 1) and round starts[j] + 1 is the first that moves it; 0 is at begin.
+ * Whether its sender is failed is decided at begin.  started, pending and the
+ * holds-every-rumor set refer to every rumor whose sender is not failed from
+ * begin on, injected or not: until the last one is in nobody holds all of
+ * them, and gs_run cannot stop GS_RUN_COVERED.  tick_99 stays an absolute
+ * round. */
+int gs_rumorset_begin_at(gs_ctx* ctx, const int64_t* senders, const int64_t* starts, size_t count);
+/* Rumor copies, cumulative over the broadcast, as of the last round gs_step or
+ * gs_run completed.  GS_EINVAL on a set without a cap (payload 0): its round
+ * kernel counts none of them; payload 64 moves the same and counts. */
+typedef struct gs_rumorset_traffic {
+  uint64_t wanted;   /* rumors the receiving ends lacked, summed over messages  */
+  uint64_t carried;  /* rumors the messages carried (<= wanted)                 */
+  uint64_t bound;    /* messages that wanted more than `payload` rumors         */
+  uint64_t reserved_;
+} gs_rumorset_traffic;
+int gs_rumorset_traffic_get(gs_ctx* ctx, gs_rumorset_traffic* out);
+
 /* Injects a peer table in place of the overlay (the `friends` slices,
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
  * Host buffers; copied.  Batched trials: trials tables back to back
