@@ -401,9 +401,24 @@ int gs_shard_info(const gs_ctx* c, uint32_t index, uint32_t* nshards, uint64_t* 
 
 void gs_destroy(gs_ctx* c) { destroy_one(c); }
 
+// A load or an overlay build writes over the table it replaces before it
+// knows whether the new one is good (the copy comes before validate_table, a
+// shard group's leader has dropped its partition by then, and an overlay that
+// ends in GS_ELIVELOCK has written half its rows): from its first touch to its
+// success the context, every group member and a push-pull shard's replica have
+// no table, and gs_broadcast_begin / gs_read_peers refuse.
+static void drop_table(gs_ctx* c) {
+  c->peers = false;
+  if (c->rs.rep) c->rs.rep->peers = false;
+  for (gs_ctx* r : c->gr.reps)
+    if (r) r->peers = false;
+  for (gs_ctx* m : c->gr.mem) drop_table(m);
+}
+
 int gs_load_peers(gs_ctx* c, const uint8_t* deg, const uint32_t* ids, uint32_t stride) {
   if (!c || !deg || !ids || stride == 0 || stride > 255) return fail(c, GS_EINVAL, "bad peer table");
   if (c->begun) return fail(c, GS_EINVAL, "peers must be loaded before gs_broadcast_begin");
+  drop_table(c);
   if (c->group && c->gtrials) {
     uint64_t off = 0;
     for (gs_ctx* m : c->gr.mem) {
@@ -436,12 +451,14 @@ int gs_load_peers_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32
     return fail(c, GS_EINVAL, "bad device peer table (stride must be in [2,255])");
   if (c->begun) return fail(c, GS_EINVAL, "peers must be loaded before gs_broadcast_begin");
   if (c->mdt) {  // a median batch: tables back to back, as gs_load_peers takes them
+    drop_table(c);
     RC(mdt_load_device(c, d_deg, d_ids, stride));
     c->peers = true;
     return GS_OK;
   }
   if (c->group || c->trials > 1)
     return fail(c, GS_EINVAL, "device tables load into one-device, one-trial contexts");
+  drop_table(c);
   CK(c, hipSetDevice(c->dev));
   c->row_slots = 0;
   RC(alloc_table(c, stride));
@@ -507,6 +524,7 @@ int gs_build_overlay(gs_ctx* c, uint64_t max_ticks, gs_window* win, size_t cap, 
                      uint64_t* final_tick) {
   if (!c) return GS_EINVAL;
   if (c->begun) return fail(c, GS_EINVAL, "overlay must be built before gs_broadcast_begin");
+  drop_table(c);
   if (c->group && c->gtrials) {
     std::vector<uint64_t> ft(c->gr.mem.size(), 0);
     std::vector<size_t> nw(c->gr.mem.size(), 0);
@@ -677,6 +695,7 @@ int gs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out) {
 int gs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap,
            size_t* nout, int32_t* status) {
   if (!c || poll == 0) return fail(c, GS_EINVAL, "poll must be >= 1");
+  if (!c->peers) return fail(c, GS_EINVAL, "load peers or build the overlay first");
   if (c->group && c->gtrials) {  // every batch runs its own trials to their stops
     std::vector<int32_t> sts(c->gr.mem.size(), 0);
     RC(par_members(c, [&](gs_ctx* m, size_t i) {

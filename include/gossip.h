@@ -477,18 +477,43 @@ int gs_rumorset_traffic_get(gs_ctx* ctx, gs_rumorset_traffic* out);
  * simulator.go:45,58).  deg[n] uint8, ids[n*stride] uint32 row-major.
  * Host buffers; copied.  Batched trials: trials tables back to back
  * (deg[trials*n], ids[trials*n*stride], ids local to their trial).  A sharded
- * context keeps only each shard's partition (gs_read_peers then fails). */
+ * context keeps only each shard's partition (gs_read_peers then fails).
+ * stride 1..255 (a window-engine context without GS_FLAG_TICK_ENGINE: at
+ * most 32); slots past a row's deg are never followed and may hold anything.
+ * Refused (GS_EINVAL): a deg above the stride ("a friends-list length exceeds
+ * the row stride") or a used slot >= n ("a friend id is >= n").  A table
+ * with both: the length is reported; batched trials, checked on the host,
+ * report whichever comes first in row order.
+ * After a refusal the context has NO table: the new table is written over
+ * the old one before it is validated, so a load that fails for any reason
+ * other than its arguments (a NULL pointer, a stride outside 1..255, a
+ * broadcast already begun: these touch nothing and keep the table) leaves the
+ * context, every member of a gs_create_multi group and a push-pull shard's
+ * replica without one.  Until the next load or overlay build that succeeds,
+ * gs_broadcast_begin and gs_run answer GS_EINVAL "load peers or build the
+ * overlay first" and gs_read_peers "no peer table". */
 int gs_load_peers(gs_ctx* ctx, const uint8_t* deg, const uint32_t* ids, uint32_t stride);
-/* Same, from device-resident buffers (copied device-to-device).  One-trial
- * contexts, and a gs_create_batch median batch (tables back to back). */
+/* Same, from device-resident buffers (copied device-to-device on the
+ * context's stream).  One-trial one-device contexts, and a gs_create_batch
+ * median batch (tables back to back); stride 2..255.  The same refusals and
+ * the same state after one: a refusal of the arguments (NULL, stride, begun,
+ * a group or a batched non-median context) keeps the table, any later one
+ * leaves the context without a table. */
 int gs_load_peers_device(gs_ctx* ctx, const void* d_deg, const void* d_ids, uint32_t stride);
-/* Copies the current table out (stride = max(fanout, fanin) after an overlay). */
+/* Copies the current table out (stride = max(fanout, fanin) after an overlay).
+ * Used slots hold the ids loaded or built; unused slots hold 0xFFFFFFFF on a
+ * window-engine context (the rows are sealed) and what was loaded elsewhere.
+ * "no peer table" before the first load or build and after a refused one. */
 int gs_read_peers(gs_ctx* ctx, uint8_t* deg, uint32_t* ids, uint32_t* stride_out);
 
 /* Replaces simulator.go:62-106,127-164 (makeup/breakup handlers, Makeup,
  * Breakup, removeFriend) and the stabilisation loop :214-235, on the GPU.
  * Writes one gs_window per non-final poll (up to cap; *nwin gets the total)
- * and the stabilising poll's tick.  GS_ELIVELOCK after max_ticks. */
+ * and the stabilising poll's tick.  GS_ELIVELOCK after max_ticks.  The build
+ * writes into the table's buffers from its first tick: a build that fails
+ * (GS_ELIVELOCK included) leaves the context without a table, as a refused
+ * gs_load_peers does; only "overlay must be built before gs_broadcast_begin"
+ * keeps the table. */
 int gs_build_overlay(gs_ctx* ctx, uint64_t max_ticks, gs_window* win, size_t cap,
                      size_t* nwin, uint64_t* final_tick);
 
