@@ -132,6 +132,41 @@ func hipTrials(devices []int32, first, trials uint32) []C.gs_trial_stats {
 	return out[:int(nout)]
 }
 
+// hipMedianBatch runs `trials` independent median-counter broadcasts (the
+// GS_MODEL_MEDIAN extension) as one batch on device 0, a workgroup per trial,
+// and returns each trial's outcome.  GS_FLAG_MEDIAN_PACKED lets N reach
+// gs_median_trials_max_n_packed (50,304 on an MI355X, so the reference's
+// default N = 50000 fits; without the flag the limit is
+// gs_median_trials_max_n, 31,104).  The flag's price is an in-degree bound
+// that gs_broadcast_begin checks; the overlay's own tables are far inside it.
+func hipMedianBatch(first, trials, k uint32) []C.gs_trial_stats {
+	runtime.LockOSThread()
+	var nmax C.uint64_t
+	hipCheck(nil, C.gs_median_trials_max_n_packed(0, &nmax))
+	if uint64(N) > uint64(nmax) {
+		panic(fmt.Sprintf("a packed median batch takes n <= %d on this device", uint64(nmax)))
+	}
+	p := hipParams()
+	p.model = C.GS_MODEL_MEDIAN
+	p.rumor_k = C.uint32_t(k)
+	p.flags = C.GS_FLAG_MEDIAN_PACKED
+	p.trial = C.uint32_t(first)
+	p.trials = C.uint32_t(trials)
+	var ctx *C.gs_ctx
+	hipCheck(nil, C.gs_create_batch(&p, &ctx))
+	defer C.gs_destroy(ctx)
+	var nwin C.size_t
+	var stab C.uint64_t
+	hipCheck(ctx, C.gs_build_overlay(ctx, 10000000, nil, 0, &nwin, &stab))
+	hipCheck(ctx, C.gs_broadcast_begin(ctx, -1))
+	var status C.int32_t
+	var nout C.size_t
+	hipCheck(ctx, C.gs_run(ctx, 10, 10000000, nil, 0, &nout, &status))
+	out := make([]C.gs_trial_stats, trials)
+	hipCheck(ctx, C.gs_trial_results(ctx, &out[0], C.size_t(trials), &nout))
+	return out[:int(nout)]
+}
+
 // hipCommID is called on rank 0 of a multi-process run; ship the bytes to
 // every rank (any transport) before hipRank.
 func hipCommID() []byte {

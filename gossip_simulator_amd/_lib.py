@@ -23,6 +23,7 @@ GS_FLAG_PP_EARLY = 16
 GS_FLAG_PP_TOPDOWN = 32
 GS_FLAG_PP_BOTTOM = 64
 GS_FLAG_PP_ANSWER = 128
+GS_FLAG_MEDIAN_PACKED = 256
 GS_MODEL_FLOOD, GS_MODEL_PUSHPULL, GS_MODEL_RUMOR, GS_MODEL_MEDIAN = 0, 1, 2, 3
 GS_RUMOR_BLIND, GS_RUMOR_COIN, GS_RUMOR_PULL = 1, 2, 4
 GS_RUN_COVERED, GS_RUN_QUIESCENT, GS_RUN_MAX_TICKS, GS_RUN_RUNNING = 0, 1, 2, -1
@@ -42,7 +43,7 @@ EXPORTS = (
     "gs_create_rank_exchange", "gs_shard_timing", "gs_trim", "gs_memory_stats",
     "gs_pp_trials_max_n", "gs_pp_trials_max_n_masked", "gs_read_removed",
     "gs_create_trials", "gs_rumor_trials_max_n", "gs_read_median_state",
-    "gs_create_batch", "gs_median_trials_max_n",
+    "gs_create_batch", "gs_median_trials_max_n", "gs_median_trials_max_n_packed",
     "gs_create_rumorset", "gs_rumorset_begin", "gs_rumorset_results", "gs_read_rumorset",
     "gs_read_rumor_column",
     "gs_rumorset_set_payload", "gs_rumorset_begin_at", "gs_rumorset_traffic_get",
@@ -188,6 +189,7 @@ def load():
         "gs_pp_trials_max_n_masked": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_rumor_trials_max_n": ([C.c_int, C.c_uint32, P(C.c_uint64)], C.c_int),
         "gs_median_trials_max_n": ([C.c_int, P(C.c_uint64)], C.c_int),
+        "gs_median_trials_max_n_packed": ([C.c_int, P(C.c_uint64)], C.c_int),
         "gs_create_rumorset": ([P(Params), C.c_uint32, P(vp)], C.c_int),
         "gs_rumorset_begin": ([ctx, P(C.c_int64), sz], C.c_int),
         "gs_rumorset_results": ([ctx, P(RumorStats), sz, P(sz)], C.c_int),

@@ -4,7 +4,8 @@
 // through the C ABI (include/gossip.h).  Durations are SIMULATED time
 // (1 tick = 1 ms, the unit of simulator.go:167) printed with Go's
 // time.Duration format; wall-clock figures go to stderr.  Additive flags
-// (-seed -trial -trials -device -peers -maxticks -model -k -batch -rumors -payload -pick -every) are not echoed in
+// (-seed -trial -trials -device -peers -maxticks -model -k -batch -packed -rumors -payload -pick -every) are not
+// echoed in
 // the parameter block, so stdout keeps the reference's shape.  -model pushpull
 // -rumors R runs R rumors from keyed senders as one rumor set
 // (gs_create_rumorset): each poll's line shows the least-covered started rumor,
@@ -16,7 +17,8 @@
 // and -model median run to their own end and add the residue and the messages
 // per node (-model median: one trial, or -batch T trials through
 // gs_create_batch, printed like the rumor model's with a stranded column: the
-// nodes still active at the trial's stop).  -trials T > 1 runs
+// nodes still active at the trial's stop; -packed sets GS_FLAG_MEDIAN_PACKED for
+// the batch, which lets n reach the default 50,000).  -trials T > 1 runs
 // T independent trials in one batched context and prints one line per trial;
 // with -model rumor (gs_create_trials) the trial lines carry the model's own
 // figures and a summary line their mean and sample standard deviation, and
@@ -320,6 +322,8 @@ int main(int argc, char** argv) {
        "2", false, "2"},
       {"batch", "int", "median model: this many independent trials trial .. trial+batch-1 in one batched context "
        "(gs_create_batch; one line per trial)", "0", false, "0"},
+      {"packed", "bool", "with -batch: 16-bit tallies (GS_FLAG_MEDIAN_PACKED), so n may reach 50,304 on an MI355X; "
+       "a table that names one node in more than 32,766 slots is refused", "false", false, "false"},
       {"blind", "bool", "rumor model: a hot node loses interest without waiting for a reply (GS_RUMOR_BLIND)",
        "false", false, "false"},
       {"coin", "bool", "rumor model: lose interest with probability 1/k per event, not after k events (GS_RUMOR_COIN)",
@@ -381,6 +385,12 @@ int main(int argc, char** argv) {
   if (median_batch && ival("gpus") > 1) {
     fprintf(stderr, "flag -batch with -gpus %s: a median batch runs on one device (GS_MODEL_MEDIAN)\n",
             find("gpus")->val.c_str());
+    usage();
+    return 2;
+  }
+  const bool median_packed = find("packed")->val == "true";
+  if (median_packed && !median_batch) {
+    fprintf(stderr, "flag -packed needs -batch (it packs the tallies of a batch of median-counter trials)\n");
     usage();
     return 2;
   }
@@ -473,6 +483,7 @@ int main(int argc, char** argv) {
             : model == "median" ? GS_MODEL_MEDIAN
                                 : GS_MODEL_FLOOD;
   if (p.model == GS_MODEL_MEDIAN) p.rumor_k = (uint32_t)rumor_k;
+  if (median_packed) p.flags |= GS_FLAG_MEDIAN_PACKED;
   const bool self_ending = p.model == GS_MODEL_RUMOR || p.model == GS_MODEL_MEDIAN;  // runs to its own end
   if (p.model == GS_MODEL_RUMOR) {
     p.rumor_k = (uint32_t)rumor_k;

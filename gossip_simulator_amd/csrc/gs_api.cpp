@@ -195,7 +195,12 @@ int gs_pp_trials_max_n_masked(int device, uint64_t* n_max) {
 
 int gs_median_trials_max_n(int device, uint64_t* n_max) {
   return trials_max_n("gs_median_trials_max_n", device, n_max, "",
-                      [&](uint64_t* lim) { return mdt_limit_error(device, lim); }, mdt_max_n);
+                      [&](uint64_t* lim) { return mdt_limit_error(device, false, lim); }, mdt_max_n);
+}
+
+int gs_median_trials_max_n_packed(int device, uint64_t* n_max) {
+  return trials_max_n("gs_median_trials_max_n_packed", device, n_max, "",
+                      [&](uint64_t* lim) { return mdt_limit_error(device, true, lim); }, mdt16_max_n);
 }
 
 int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max) {
@@ -409,6 +414,7 @@ void gs_destroy(gs_ctx* c) { destroy_one(c); }
 // no table, and gs_broadcast_begin / gs_read_peers refuse.
 static void drop_table(gs_ctx* c) {
   c->peers = false;
+  c->named_ok = false;  // (a packed median batch: the next table is counted at its first begin)
   if (c->rs.rep) c->rs.rep->peers = false;
   for (gs_ctx* r : c->gr.reps)
     if (r) r->peers = false;

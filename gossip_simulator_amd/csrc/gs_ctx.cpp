@@ -733,13 +733,15 @@ int create_one(const gs_params* params, int device, bool shard, uint32_t G, uint
   int rc = check_params(params, rumor_trials, median_trials, why);
   if (!rc) rc = check_ppt_n(params, device, why, &pl);
   if (!rc) rc = check_rmt_n(params, device, why, &rpl);
-  if (!rc) rc = check_mdt_n(params, device, why, &mpl);
+  bool packed = false;
+  if (!rc) rc = check_mdt_n(params, median_trials, device, why, &mpl, &packed);
   if (!rc) {
     gs_ctx* c = new gs_ctx();
     c->rset = rumorset != 0;  // a rumor set (gs_create_rumorset checked the rest)
     c->rumors = rumorset;
     if (mpl.block) {  // batched median trials: the plan check_mdt_n made for this device
       c->mdt = true;
+      c->mdt16 = packed;
       c->mplan = mpl;
     }
     if (rpl.block) {  // batched rumor trials: the plan check_rmt_n made for this device

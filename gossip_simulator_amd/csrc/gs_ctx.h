@@ -21,7 +21,7 @@
 #include "gossip.h"
 #include "gs_comm.h"
 #include "gs_internal.h"
-#include "gs_mdt_plan.h"
+#include "gs_mdt16_plan.h"
 #include "gs_median.h"
 #include "gs_ppt_plan.h"
 #include "gs_rmt_plan.h"
@@ -257,6 +257,9 @@ struct gs_ctx {
   // batched median trials (gs_create_batch; gs_median_trials.hip): a workgroup per trial
   bool mdt = false;
   gs::MdtPlan mplan{};
+  // GS_FLAG_MEDIAN_PACKED at create: mplan is gs_mdt16_plan.h's.  named_ok: the table in place has
+  // passed the in-degree guard (set by the first gs_broadcast_begin after it entered)
+  bool mdt16 = false, named_ok = false;
   // concurrent push-pull rumors (gs_create_rumorset; gs_rumorset.hip): `rumors` bits per node
   bool rset = false;
   uint32_t rumors = 0;
@@ -480,8 +483,8 @@ int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out,
                int32_t* status);
 int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords);
 int median_read_state(gs_ctx* c, uint8_t* st, size_t n);
-std::string mdt_limit_error(int device, uint64_t* lim);
-int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl);
+std::string mdt_limit_error(int device, bool packed, uint64_t* lim);
+int check_mdt_n(const gs_params* p, bool median_trials, int device, std::string& why, MdtPlan* pl, bool* packed);
 int mdt_load_device(gs_ctx* c, const void* d_deg, const void* d_ids, uint32_t stride);
 
 // gs_rumorset_host.cpp

@@ -641,16 +641,24 @@ struct MdtState {
   int32_t kd;
   Key key;
 };
-// Per-workgroup LDS the device grants k_mdt_rounds (bytes).  On an error
-// *where (may be null) names the HIP call that failed.
-hipError_t mdt_lds_limit(int device, uint64_t* limit, const char** where = nullptr);
+// `packed` below: the context's plan is gs_mdt16_plan.h's (GS_FLAG_MEDIAN_PACKED;
+// DESIGN.md section 4.8.2) and its rounds are k_mdt16_rounds'.
+// Per-workgroup LDS the device grants k_mdt_rounds or k_mdt16_rounds (bytes).
+// On an error *where (may be null) names the HIP call that failed.
+hipError_t mdt_lds_limit(int device, bool packed, uint64_t* limit, const char** where = nullptr);
 // Opt both instantiations (masked and not) in to lds_bytes > 64 KiB of dynamic LDS on `device`.
-hipError_t mdt_prepare(int device, uint32_t lds_bytes);
+hipError_t mdt_prepare(int device, bool packed, uint32_t lds_bytes);
 // Every trial's sender (`node`, or ~0u: the trial's keyed sender) B-1 unless
 // failed; st zeroed by the caller.  started[trial] = 1 if it was informed.
 hipError_t mdt_seed(const MdtState& s, uint32_t node, uint32_t* started, hipStream_t st);
 // Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow); tstat row k = round t0 + k.
-hipError_t mdt_rounds(const MdtState& s, uint32_t t0, uint32_t rounds, hipStream_t st);
+hipError_t mdt_rounds(const MdtState& s, bool packed, uint32_t t0, uint32_t rounds, hipStream_t st);
+// The packed tallies' in-degree guard over trials [t_lo, t_hi): cnt[(t_hi - t_lo)
+// << tlog] (zeroed by the caller) gets, per node, the used slots of its trial's
+// table that name it; *worst (~0 from the caller) the lowest index into cnt
+// whose count is above `bound`.
+hipError_t mdt_count_named(const MdtState& s, uint32_t t_lo, uint32_t t_hi, uint32_t bound, uint32_t* cnt,
+                           unsigned long long* worst, hipStream_t st);
 // Device tables back to back (ids local to their trial) into the zeroed padded
 // id space; *err: 1 = a row longer than the stride, 2 = a friend id >= n.
 hipError_t mdt_spread_table(const uint8_t* deg, const uint32_t* ids, uint32_t n, uint32_t trials, uint32_t tlog,

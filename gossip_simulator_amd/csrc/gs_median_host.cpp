@@ -52,6 +52,46 @@ MdtState mdt_state(const gs_ctx* c) {
   return m;
 }
 
+// The packed tallies' in-degree guard, once per
+// table: with n <= kMdt16MaxNamed the callers of a round are too few to
+// overflow a field whatever the table; past that, no node may be named by more
+// than kMdt16MaxNamed used slots of its trial's table (slots, not rows: a
+// conservative count).  Counted on the device a chunk of trials at a time, a
+// u32 per padded node, in scratch that is released before the answer.
+int mdt_check_named(gs_ctx* c, const MdtState& ms) {
+  if (c->p.n <= kMdt16MaxNamed) return GS_OK;
+  const uint64_t per = 1ull << c->tlog;
+  const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c->trials, (64ull << 20) / (per * 4)));
+  uint32_t* cnt = nullptr;
+  if (dev_malloc((void**)&cnt, (size_t)chunk * per * 4 + 8) != hipSuccess)
+    return fail(c, GS_ENOMEM, "cannot allocate the in-degree count of a packed median batch");
+  unsigned long long* d_worst = (unsigned long long*)(cnt + (size_t)chunk * per);
+  unsigned long long worst = ~0ull;
+  uint32_t count = 0, t_lo = 0;
+  hipError_t e = hipSuccess;
+  for (; t_lo < c->trials && e == hipSuccess && worst == ~0ull; t_lo += chunk) {
+    const uint32_t t_hi = std::min<uint32_t>(c->trials, t_lo + chunk);
+    e = hipMemsetAsync(cnt, 0, (size_t)(t_hi - t_lo) * per * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_worst, 0xFF, 8, c->stream);
+    if (e == hipSuccess) e = mdt_count_named(ms, t_lo, t_hi, kMdt16MaxNamed, cnt, d_worst, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&worst, d_worst, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && worst != ~0ull) {
+      e = hipMemcpy(&count, cnt + worst, 4, hipMemcpyDeviceToHost);
+      worst += (uint64_t)t_lo * per;
+    }
+  }
+  (void)dev_free(cnt);
+  CK(c, e);
+  if (worst == ~0ull) return GS_OK;
+  return fail(c, GS_EINVAL,
+              "GS_FLAG_MEDIAN_PACKED keeps 16-bit tallies: trial " + std::to_string(c->p.trial + (worst >> c->tlog)) +
+                  " (index " + std::to_string(worst >> c->tlog) + "): node " + std::to_string(worst & (per - 1)) +
+                  " is named by " + std::to_string(count) + " used slots of its table, more than the " +
+                  std::to_string(kMdt16MaxNamed) + " a packed batch takes; load another table, or run the batch " +
+                  "without the flag (n <= gs_median_trials_max_n)");
+}
+
 // Every trial's sender (k_mdt_seed): the trials that started have one informed,
 // active node.  The started flags use the first words of the counter rows,
 // free between broadcasts.
@@ -59,6 +99,10 @@ int mdt_begin(gs_ctx* c, uint64_t sender) {
   CK(c, hipSetDevice(c->dev));
   const uint32_t T = c->trials;
   const MdtState ms = mdt_state(c);
+  if (c->mdt16 && !c->named_ok) {
+    RC(mdt_check_named(c, ms));
+    c->named_ok = true;
+  }
   CK(c, hipMemsetAsync(c->md.st.p, 0, c->st.n, c->stream));
   CK(c, mdt_seed(ms, (uint32_t)sender, c->bt.d_tstat, c->stream));
   CK(c, hipMemcpyAsync(c->bt.h_tstat, c->bt.d_tstat, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
@@ -78,7 +122,7 @@ int mdt_begin(gs_ctx* c, uint64_t sender) {
 // and a row's messages = the active ends of the round's connections.
 TrialLaunch mdt_launch(gs_ctx* c) {
   return [c, ms = mdt_state(c)](uint64_t t0, uint32_t batch) -> int {
-    CK(c, mdt_rounds(ms, (uint32_t)t0, batch, c->stream));
+    CK(c, mdt_rounds(ms, c->mdt16, (uint32_t)t0, batch, c->stream));
     return GS_OK;
   };
 }
@@ -117,9 +161,9 @@ int mdt_read_state(gs_ctx* c, uint8_t* st, size_t n) {
 }  // namespace
 
 // mdt_lds_limit with its failure in words ("" on success).
-std::string mdt_limit_error(int device, uint64_t* lim) {
+std::string mdt_limit_error(int device, bool packed, uint64_t* lim) {
   const char* where = "";
-  const hipError_t e = mdt_lds_limit(device, lim, &where);
+  const hipError_t e = mdt_lds_limit(device, packed, lim, &where);
   return trial_limit_error(where, device, e);
 }
 
@@ -128,29 +172,42 @@ std::string mdt_limit_error(int device, uint64_t* lim) {
 // parameters, after check_params and before any device state is set up; *pl
 // gets the plan (block 0: not such a context).  With no device to ask the
 // parameters were valid as far as they can be checked: GS_EDEVICE.
-int check_mdt_n(const gs_params* p, int device, std::string& why, MdtPlan* pl) {
+// GS_FLAG_MEDIAN_PACKED is read here and nowhere else: gs_create_batch
+// (median_trials) makes the batch on the packed plan (*packed); every other
+// create and model never looks at the bit.
+int check_mdt_n(const gs_params* p, bool median_trials, int device, std::string& why, MdtPlan* pl, bool* packed) {
   *pl = MdtPlan{};
+  *packed = false;
   if (p->trials <= 1 || p->model != GS_MODEL_MEDIAN) return GS_OK;
+  const bool p16 = median_trials && (p->flags & GS_FLAG_MEDIAN_PACKED) != 0;
   RC(trial_device_check(device, why));
   uint64_t lim = 0;
-  why = mdt_limit_error(device, &lim);
+  why = mdt_limit_error(device, p16, &lim);
   if (!why.empty()) {
     (void)hipGetLastError();
     return GS_EDEVICE;
   }
-  const MdtPlan plan = mdt_plan(p->n, lim);
+  const MdtPlan plan = p16 ? mdt16_plan(p->n, lim) : mdt_plan(p->n, lim);
+  if (!plan.fits && p16) {
+    why = "a packed median batch (GS_FLAG_MEDIAN_PACKED) keeps a trial's state bytes, 16-bit tallies and flag sets "
+          "in one workgroup's LDS: n must be <= " + std::to_string(mdt16_max_n(lim)) +
+          " on this device (gs_median_trials_max_n_packed), not " + std::to_string(p->n) +
+          "; a one-trial context (gs_create) has no such limit";
+    return GS_EINVAL;
+  }
   if (!plan.fits) {
     why = "batched median trials keep a trial's state bytes, tallies and flag sets in one workgroup's LDS: n must "
           "be <= " + std::to_string(mdt_max_n(lim)) + " on this device (gs_median_trials_max_n), not " +
           std::to_string(p->n) + "; a one-trial context (gs_create) has no such limit";
     return GS_EINVAL;
   }
-  if (plan.lds_bytes > 65536 && mdt_prepare(device, (uint32_t)plan.lds_bytes) != hipSuccess) {
+  if (plan.lds_bytes > 65536 && mdt_prepare(device, p16, (uint32_t)plan.lds_bytes) != hipSuccess) {
     (void)hipGetLastError();
     why = "cannot raise the trial-resident median kernel's dynamic LDS limit";
     return GS_EDEVICE;
   }
   *pl = plan;
+  *packed = p16;
   return GS_OK;
 }
 

@@ -26,6 +26,12 @@
 // its own byte, behind a barrier; the commit also zeroes the lane's diff and
 // the wave's own flag words.  Nothing depends on wave or atomic order.
 //
+// GS_FLAG_MEDIAN_PACKED: k_mdt16_rounds is the same
+// code on the plan of gs_mdt16_plan.h, where diff is a 16-bit field per node,
+// two to a 32-bit word.  Only where a +-1 goes and how the commit reads and
+// clears it differ (Tally32, Tally16); a table whose in-degrees could overflow
+// a field is refused before the first round (k_mdt_count_named).
+//
 // Layout (the batched layout of gs_ctx.cpp): global node trial << tlog | v,
 // deg, rows and state bytes at that index, the trial's words at word offset
 // (trial << tlog) / 64 (tlog >= 14: whole words, disjoint per trial).  Padding
@@ -34,7 +40,7 @@
 // s.crash (read-only, L2-resident): the kMasked instantiation; the other has
 // no trace of it.
 #include "gs_internal.h"
-#include "gs_mdt_plan.h"
+#include "gs_mdt16_plan.h"
 #include "gs_wave.h"
 
 namespace gs {
@@ -44,12 +50,13 @@ namespace {
 static_assert(kMdtCounters <= kTStatFields && TS_MSGS < kTStatFields && TS_HOT < kTStatFields,
               "a tstat row holds the round's counters");
 static_assert(kMdtWordBytes == 336 && kMdtScratchBytes == 320, "the plan DESIGN.md section 4.8.1 states");
+static_assert(kMdt16WordBytes == 208, "the plan DESIGN.md section 4.8.2 states");
 
 constexpr uint32_t kDone = 255;  // gs_median.h's kMedianDone
 
 // One trial's LDS (mdt_plan's layout) and its slot of the global arrays.
 struct MdtTrial {
-  int* diff;                       // [64 W]
+  int* diff;                       // [64 W]; packed: u16[64 W], seen as u32[32 W] (gs_mdt16_plan.h)
   unsigned long long *gotb, *gotc; // [W]
   uint32_t* scratch;               // [kMdtCounters][nwaves]
   uint8_t* st;                     // [64 W]
@@ -61,9 +68,39 @@ struct MdtTrial {
 
 __device__ __forceinline__ bool active(uint32_t s) { return s != 0 && s != kDone; }
 
+// Where a +-1 on a node's tally goes and how the commit reads and clears it:
+// all that the two plans' rounds differ in.  kDiff8: the tallies' 8-byte words
+// per 64 nodes; kInit8: such a word with every tally at ge - lt = 0.
+struct Tally32 {  // gs_mdt_plan.h: a signed word per node
+  static constexpr uint32_t kDiff8 = 32;
+  static constexpr unsigned long long kInit8 = 0;
+  static __device__ __forceinline__ void add(const MdtTrial& T, uint32_t v, bool up) {
+    atomicAdd(&T.diff[v], up ? 1 : -1);
+  }
+  static __device__ __forceinline__ int take(const MdtTrial& T, uint32_t v) {
+    const int df = T.diff[v];
+    if (df) T.diff[v] = 0;
+    return df;
+  }
+};
+// gs_mdt16_plan.h: a 16-bit field per node, two to a word.  The round half
+// touches a word with 32-bit LDS atomics only, the commit half with 16-bit
+// accesses to the lane's own half only, and a workgroup barrier is between
+// the two: no access of one kind is ever concurrent with one of the other.
+struct Tally16 {
+  static constexpr uint32_t kDiff8 = 16;
+  static constexpr unsigned long long kInit8 = ((unsigned long long)kMdt16Init << 32) | kMdt16Init;
+  static __device__ __forceinline__ void add(const MdtTrial& T, uint32_t v, bool up) {
+    atomicAdd((uint32_t*)T.diff + mdt16_word(v), mdt16_delta(v, up));
+  }
+  static __device__ __forceinline__ int take(const MdtTrial& T, uint32_t v) {
+    return mdt16_take((uint32_t*)T.diff, v);
+  }
+};
+
 // k_median_round on the trial's LDS: every live node with a friend that is not
 // done calls; both ends of a connection go to diff, gotb and gotc.
-template <bool kMasked>
+template <bool kMasked, class Tally>
 __device__ __forceinline__ void mdt_round(const MdtState& s, const MdtTrial& T, uint32_t t, uint32_t& fired,
                                           uint32_t& sent, uint32_t& msgs) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -90,9 +127,9 @@ __device__ __forceinline__ void mdt_round(const MdtState& s, const MdtTrial& T, 
           if (au) {
             if (su > k) ownc = sv <= k;         // a C partner (only an A or B node keeps count)
             else if (sv == 0) ownb = true;      // an A caller: a B partner
-            else if (sv <= k) atomicAdd(&T.diff[v], su >= sv ? 1 : -1);
+            else if (sv <= k) Tally::add(T, v, su >= sv);
           } else if (su == 0 && av && sv <= k) {
-            atomicAdd(&T.diff[v], -1);
+            Tally::add(T, v, false);
           }
           // u's end: its partner v.  Only an A or B callee keeps count.
           if (su <= k) {
@@ -105,7 +142,7 @@ __device__ __forceinline__ void mdt_round(const MdtState& s, const MdtTrial& T, 
                 if (!(*f & ubit)) atomicOr(f, ubit);
               }
             } else {  // u in B-su, v in A or B-sv
-              atomicAdd(&T.diff[u], sv >= su ? 1 : -1);
+              Tally::add(T, u, sv >= su);
             }
           }
         }
@@ -123,6 +160,7 @@ __device__ __forceinline__ void mdt_round(const MdtState& s, const MdtTrial& T, 
 // k_median_commit per word: the transition table, the lane's diff and the
 // wave's flag words zeroed; newly = the nodes informed this round, nact = the
 // active nodes after it.
+template <class Tally>
 __device__ __forceinline__ void mdt_commit(const MdtState& s, const MdtTrial& T, uint32_t& newly, uint32_t& nact) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const uint32_t k = s.k;
@@ -136,8 +174,7 @@ __device__ __forceinline__ void mdt_commit(const MdtState& s, const MdtTrial& T,
       if (c) s1 = k + 1;
       else if ((gb >> lane) & 1) s1 = 1;
     } else if (s0 <= k) {
-      const int df = T.diff[v];
-      if (df) T.diff[v] = 0;
+      const int df = Tally::take(T, v);
       if (c) s1 = k + 1;
       else if (df > 0) s1 = s0 < k ? s0 + 1 : k + 1;
     } else if (s0 != kDone) {
@@ -154,8 +191,6 @@ __device__ __forceinline__ void mdt_commit(const MdtState& s, const MdtTrial& T,
   }
 }
 
-}  // namespace
-
 // Rounds t0 .. t0 + rounds - 1 (rounds <= kMaxWindow) of every trial; row k of
 // a trial's tstat block gets round t0 + k's counters (TS_MSGS = the active
 // ends of the round's connections, TS_HOT = the active nodes after the round).
@@ -169,19 +204,20 @@ __device__ __forceinline__ void mdt_commit(const MdtState& s, const MdtTrial& T,
 //
 // A trial is never skipped: after its own end its A nodes still call and are
 // counted, as in the one-trial context.
-template <bool kMasked>
-__global__ __launch_bounds__(kMdtMaxBlock) void k_mdt_rounds(const MdtState s, uint32_t t0, uint32_t rounds) {
+template <bool kMasked, class Tally>
+__device__ __forceinline__ void mdt_trial_rounds(const MdtState s, uint32_t t0, uint32_t rounds) {
   extern __shared__ unsigned long long mdt_lds[];
+  constexpr uint32_t kD8 = Tally::kDiff8;
   const uint32_t trial = blockIdx.x;
   uint32_t* __restrict__ rows = s.tstat + (size_t)trial * kMaxWindow * kTStatFields;
   const uint32_t W = (s.n + 63) >> 6;
   const uint64_t base = (uint64_t)trial << s.tlog;
   MdtTrial T;
   T.W = W;
-  T.diff = (int*)mdt_lds;                      // 32 W words of 8 bytes
-  T.gotb = mdt_lds + 32 * (size_t)W;
-  T.gotc = mdt_lds + 33 * (size_t)W;
-  T.scratch = (uint32_t*)(mdt_lds + 34 * (size_t)W);
+  T.diff = (int*)mdt_lds;                      // kD8 W words of 8 bytes
+  T.gotb = mdt_lds + kD8 * (size_t)W;
+  T.gotc = mdt_lds + (kD8 + 1) * (size_t)W;
+  T.scratch = (uint32_t*)(mdt_lds + (kD8 + 2) * (size_t)W);
   T.st = (uint8_t*)(T.scratch + kMdtCounters * (kMdtMaxBlock / 64));
   T.deg = s.deg + base;
   T.ids = s.ids + base * s.stride;
@@ -193,15 +229,16 @@ __global__ __launch_bounds__(kMdtMaxBlock) void k_mdt_rounds(const MdtState s, u
   unsigned long long* ls8 = (unsigned long long*)T.st;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
 
-  for (uint32_t i = threadIdx.x; i < 34 * W; i += blockDim.x) mdt_lds[i] = 0;  // diff, gotb, gotc
+  for (uint32_t i = threadIdx.x; i < (kD8 + 2) * W; i += blockDim.x)  // diff, gotb, gotc
+    mdt_lds[i] = i < kD8 * W ? Tally::kInit8 : 0ull;
   for (uint32_t i = threadIdx.x; i < 8 * W; i += blockDim.x) ls8[i] = gs8[i];
   __syncthreads();
   for (uint32_t r = 0; r < rounds; ++r) {
     const uint32_t t = t0 + r;
     uint32_t fired = 0, sent = 0, msgs = 0, newly = 0, nact = 0;
-    mdt_round<kMasked>(s, T, t, fired, sent, msgs);
+    mdt_round<kMasked, Tally>(s, T, t, fired, sent, msgs);
     __syncthreads();
-    mdt_commit(s, T, newly, nact);
+    mdt_commit<Tally>(s, T, newly, nact);
     const uint32_t v5[kMdtCounters] = {fired, sent, msgs, newly, nact};
 #pragma unroll
     for (uint32_t i = 0; i < kMdtCounters; ++i) {
@@ -230,6 +267,21 @@ __global__ __launch_bounds__(kMdtMaxBlock) void k_mdt_rounds(const MdtState s, u
     const unsigned long long inf = __ballot(T.st[(w << 6) + lane] != 0);
     if (lane == 0) gw[w] = inf;
   }
+}
+
+}  // namespace
+
+template <bool kMasked>
+__global__ __launch_bounds__(kMdtMaxBlock) void k_mdt_rounds(const MdtState s, uint32_t t0, uint32_t rounds) {
+  mdt_trial_rounds<kMasked, Tally32>(s, t0, rounds);
+}
+
+// k_mdt_rounds on the packed plan (gs_mdt16_plan.h):
+// the same rounds with 16-bit tallies, exact for the tables mdt_count_named
+// lets through.
+template <bool kMasked>
+__global__ __launch_bounds__(kMdtMaxBlock) void k_mdt16_rounds(const MdtState s, uint32_t t0, uint32_t rounds) {
+  mdt_trial_rounds<kMasked, Tally16>(s, t0, rounds);
 }
 
 // The sender of every trial: `node` in each, or (~0u) the trial's own keyed
@@ -277,34 +329,73 @@ __global__ void k_mdt_spread(const uint8_t* __restrict__ deg, const uint32_t* __
   }
 }
 
+// The packed tallies' in-degree guard, over the
+// padded nodes of trials [t_lo, t_hi): cnt[g - (t_lo << tlog)] = the used slots
+// of g's trial that name g.  Slots, not rows: a row that names a node twice
+// calls it at most once a round, so the count is an upper bound on the callers.
+__global__ void k_mdt_count_named(const MdtState s, uint32_t t_lo, uint32_t t_hi, uint32_t* __restrict__ cnt) {
+  const uint64_t lo = (uint64_t)t_lo << s.tlog, total = ((uint64_t)t_hi << s.tlog) - lo;
+  const uint32_t tmask = (uint32_t)((1ull << s.tlog) - 1);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t g = lo + i;
+    if ((g & tmask) >= s.n) continue;  // padding
+    const uint32_t d = s.deg[g];
+    for (uint32_t j = 0; j < d && j < s.stride; ++j) {
+      const uint32_t u = s.ids[g * s.stride + j] & tmask;
+      if (u < s.n) atomicAdd(&cnt[(i & ~(uint64_t)tmask) + u], 1u);
+    }
+  }
+}
+
+// *worst = the lowest index into cnt whose count is above `bound` (~0: none).
+__global__ void k_mdt_worst_named(const uint32_t* __restrict__ cnt, uint64_t total, uint32_t bound,
+                                  unsigned long long* worst) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x)
+    if (cnt[i] > bound) atomicMin(worst, (unsigned long long)i);
+}
+
 namespace {
 
-const void* rounds_kernel(bool masked) {
+const void* rounds_kernel(bool packed, bool masked) {
+  if (packed) return masked ? (const void*)k_mdt16_rounds<true> : (const void*)k_mdt16_rounds<false>;
   return masked ? (const void*)k_mdt_rounds<true> : (const void*)k_mdt_rounds<false>;
 }
 
 }  // namespace
 
-// What the device grants one workgroup of k_mdt_rounds (trial_lds_limit,
-// gs_trials_host.cpp).  (The masked instantiation has the same plan: the mask
-// is not in LDS.)
-hipError_t mdt_lds_limit(int device, uint64_t* limit, const char** where) {
-  return trial_lds_limit(device, rounds_kernel(false), limit, where);
+// What the device grants one workgroup of k_mdt_rounds or k_mdt16_rounds
+// (trial_lds_limit, gs_trials_host.cpp).  (The masked instantiation has the
+// same plan: the mask is not in LDS.)
+hipError_t mdt_lds_limit(int device, bool packed, uint64_t* limit, const char** where) {
+  return trial_lds_limit(device, rounds_kernel(packed, false), limit, where);
 }
 
-hipError_t mdt_prepare(int device, uint32_t lds_bytes) {
-  const void* f[] = {rounds_kernel(false), rounds_kernel(true)};
+hipError_t mdt_prepare(int device, bool packed, uint32_t lds_bytes) {
+  const void* f[] = {rounds_kernel(packed, false), rounds_kernel(packed, true)};
   return trial_raise_lds(device, f, 2, lds_bytes);
 }
 
-// s.crash set: the masked instantiation (the same LDS).
-hipError_t mdt_rounds(const MdtState& s, uint32_t t0, uint32_t rounds, hipStream_t st) {
+// s.crash set: the masked instantiation (the same LDS).  The plan checked is
+// the one the context was made with.
+hipError_t mdt_rounds(const MdtState& s, bool packed, uint32_t t0, uint32_t rounds, hipStream_t st) {
   if (rounds == 0) return hipSuccess;
   if (rounds > kMaxWindow || s.block == 0 || s.block > kMdtMaxBlock || s.lds_bytes == 0) return hipErrorInvalidValue;
-  if (mdt_plan(s.n, s.lds_bytes).lds_bytes != s.lds_bytes) return hipErrorInvalidValue;  // the kernel's own pointers
+  const MdtPlan plan = packed ? mdt16_plan(s.n, s.lds_bytes) : mdt_plan(s.n, s.lds_bytes);
+  if (plan.lds_bytes != s.lds_bytes) return hipErrorInvalidValue;  // the kernel's own pointers
   MdtState arg = s;
   void* args[] = {&arg, &t0, &rounds};
-  return hipLaunchKernel(rounds_kernel(s.crash != nullptr), dim3(s.trials), dim3(s.block), args, s.lds_bytes, st);
+  return hipLaunchKernel(rounds_kernel(packed, s.crash != nullptr), dim3(s.trials), dim3(s.block), args, s.lds_bytes,
+                         st);
+}
+
+hipError_t mdt_count_named(const MdtState& s, uint32_t t_lo, uint32_t t_hi, uint32_t bound, uint32_t* cnt,
+                           unsigned long long* worst, hipStream_t st) {
+  if (t_lo >= t_hi || t_hi > s.trials) return hipErrorInvalidValue;
+  const uint64_t total = (uint64_t)(t_hi - t_lo) << s.tlog;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_mdt_count_named, dim3(blocks), dim3(256), 0, st, s, t_lo, t_hi, cnt);
+  hipLaunchKernelGGL(k_mdt_worst_named, dim3(blocks), dim3(256), 0, st, cnt, total, bound, worst);
+  return hipGetLastError();
 }
 
 hipError_t mdt_seed(const MdtState& s, uint32_t node, uint32_t* started, hipStream_t st) {

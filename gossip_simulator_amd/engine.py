@@ -49,6 +49,10 @@ class Config:
     trials: int = 1         # batched independent trials trial .. trial+trials-1 (config C3): flood and
                             # push-pull through Simulator(cfg), the rumor model too through
                             # Simulator.batch(cfg), every model through Simulator.median_batch(cfg)
+    median_packed: bool = False  # Simulator.median_batch of model "median" with trials > 1: 16-bit
+                                 # tallies (GS_FLAG_MEDIAN_PACKED), n up to median_trials_max_n(packed=True);
+                                 # same results; a table in which some node is named by more than
+                                 # 32,766 used slots is refused at broadcast_begin when n > 32,766
     pp_l2_only: bool = False  # push-pull: force the no-LDS summary path (tests)
     pp_rounds: str = "auto"   # push-pull: "auto" (sparse early rounds while |I| <= n/256, dense
                               # rounds bottom-up once |I| >= 96n/256), "dense" (every round streams the
@@ -72,7 +76,8 @@ class Config:
             (_lib.GS_FLAG_PP_EARLY if self.pp_rounds == "early" else 0) | \
             (_lib.GS_FLAG_PP_TOPDOWN if self.pp_rounds == "topdown" else 0) | \
             (_lib.GS_FLAG_PP_BOTTOM if self.pp_rounds == "bottom" else 0) | \
-            (_lib.GS_FLAG_PP_ANSWER if self.pp_rounds == "answer" else 0)
+            (_lib.GS_FLAG_PP_ANSWER if self.pp_rounds == "answer" else 0) | \
+            (_lib.GS_FLAG_MEDIAN_PACKED if self.median_packed else 0)
 
     def to_params(self) -> Params:
         p = Params()
@@ -171,9 +176,14 @@ class Simulator:
     def median_batch(cls, cfg: Config):
         """cfg.trials trials at once on cfg.device through gs_create_batch: what
         Simulator.batch(cfg) makes, and for model="median" with trials > 1 a
-        batched median context (n <= median_trials_max_n(); the default n =
-        50,000 does not fit: use Simulator(cfg) per trial there).  Every call
-        takes the batched layouts, and median_state() is [trials, n]."""
+        batched median context.  n <= median_trials_max_n() (31,104 on an
+        MI355X); with cfg.median_packed n <= median_trials_max_n(packed=True)
+        (50,304 there, so the default n = 50,000 fits): the same results from
+        16-bit tallies, which take every table of n <= 32,766 nodes and past
+        that only tables in which no node is named by more than 32,766 used
+        slots (broadcast_begin refuses the others and names the node; the
+        overlay's own tables are far inside the bound).  Every call takes the
+        batched layouts, and median_state() is [trials, n]."""
         return cls(cfg, _batch="median")
 
     @classmethod
@@ -536,17 +546,19 @@ def rumor_trials_max_n(mode=0, device: int = 0) -> int:
     return int(out.value)
 
 
-def median_trials_max_n(device: int = 0) -> int:
+def median_trials_max_n(device: int = 0, packed: bool = False) -> int:
     """Largest n a batched median context (Simulator.median_batch,
     model="median", trials > 1) may have on `device`
     (gs_median_trials_max_n): the trial's state bytes, tallies and flag sets
-    live in one workgroup's LDS."""
+    live in one workgroup's LDS.  packed: with Config.median_packed
+    (gs_median_trials_max_n_packed)."""
     L = _lib.load()
     out = C.c_uint64(0)
-    rc = L.gs_median_trials_max_n(int(device), C.byref(out))
+    name = "gs_median_trials_max_n_packed" if packed else "gs_median_trials_max_n"
+    rc = getattr(L, name)(int(device), C.byref(out))
     if rc != 0:
         why = L.gs_last_error(None).decode(errors="replace")
-        raise GossipError(rc, "gs_median_trials_max_n failed" + (f" ({why})" if why and why != "NULL context" else ""))
+        raise GossipError(rc, name + " failed" + (f" ({why})" if why and why != "NULL context" else ""))
     return int(out.value)
 
 

@@ -56,6 +56,12 @@ enum {
 #define GS_FLAG_PP_ANSWER 128u /* push-pull: every dense round below the bottom-up threshold pull-answer
                                 * (informed nodes answer the pulls among their in-edges; the default
                                 * does too unless GS_PP_ANSWER256 is set); same results, for tests */
+#define GS_FLAG_MEDIAN_PACKED 256u /* gs_create_batch with GS_MODEL_MEDIAN and trials > 1: the batch keeps
+                                * 16-bit tallies (208 B per 64 nodes, not 336), so n may reach
+                                * gs_median_trials_max_n_packed(), 50,304 on an MI355X; the price is the
+                                * in-degree bound checked at gs_broadcast_begin (below, gs_create_batch).
+                                * Read at that create only: gs_set_flags does not switch a live context,
+                                * and every other create and model never looks at the bit.  Same results */
 
 /* Dissemination model (gs_params.model). */
 #define GS_MODEL_FLOOD 0u    /* the reference: every receipt re-broadcasts to all friends (simulator.go:107-149) */
@@ -109,7 +115,9 @@ enum {
                               * short counter strands some nodes this way: DESIGN.md section 4.8).
                               * One trial on one device through gs_create; gs_create_batch is the
                               * batch of trials (one workgroup per trial, the trial's state in LDS,
-                              * so n <= gs_median_trials_max_n()).  The
+                              * so n <= gs_median_trials_max_n(), or with GS_FLAG_MEDIAN_PACKED
+                              * n <= gs_median_trials_max_n_packed(); DESIGN.md sections 4.8.1,
+                              * 4.8.2).  The
                               * four other creates keep refusing: gs_create with trials > 1,
                               * gs_create_trials, gs_create_multi and gs_create_rank[_exchange]
                               * answer GS_EINVAL */
@@ -354,8 +362,22 @@ int gs_rumor_trials_max_n(int device, uint32_t rumor_mode, uint64_t* n_max);
  * (rumor_k 1..127, the 31-bit id space, n >= 1): bad parameters answer
  * GS_EINVAL with the reason in gs_last_error(NULL) even where no device is
  * visible, valid ones then answer GS_EDEVICE.  n past gs_median_trials_max_n()
- * answers GS_EINVAL and names the limit (about 31,000 on an MI355X: the
- * reference's default n = 50,000 does not fit; use a one-trial context there).
+ * answers GS_EINVAL and names the limit (31,104 on an MI355X).  The reference's
+ * default n = 50,000 needs GS_FLAG_MEDIAN_PACKED in params.flags: the batch
+ * then keeps a 16-bit tally per node, two to a word, n may reach
+ * gs_median_trials_max_n_packed() (50,304 on an MI355X; a larger n answers
+ * GS_EINVAL and names that limit), and every result is the same, at any n.
+ * What the flag costs is an in-degree bound: the tallies are exact only while
+ * no node has more than 32,767 partners in a round.  With n <= 32,766 that
+ * holds for every table.  Past it, the first gs_broadcast_begin after a table
+ * entered (gs_load_peers, gs_load_peers_device, gs_build_overlay) counts, on
+ * the device, the used slots of each trial's table that name each node --
+ * slots, not rows, which is conservative: a row that names a node twice calls
+ * it once -- and if some node is named by more than 32,766 it answers
+ * GS_EINVAL; gs_last_error names the trial, the node, its count and the
+ * bound.  The table is kept and the context stays usable: load another table
+ * and begin again.  The overlay's own tables (fanin 6) are far inside the
+ * bound.
  * The batched context takes the usual calls with the batched layouts
  * (gs_load_peers and gs_load_peers_device: tables back to back;
  * gs_build_overlay: the batch's own overlays; gs_set_failed: one mask per
@@ -376,6 +398,9 @@ int gs_create_batch(const gs_params* params, gs_ctx** out);
  * with GS_EINVAL.  A failure mask does not lower it.  GS_EDEVICE where the
  * device cannot be asked. */
 int gs_median_trials_max_n(int device, uint64_t* n_max);
+/* The same for a batch made with GS_FLAG_MEDIAN_PACKED: a state byte and a
+ * 16-bit tally per node and two bitsets (208 B per 64 nodes). */
+int gs_median_trials_max_n_packed(int device, uint64_t* n_max);
 
 /* ---- concurrent rumors for push-pull ----
  * Who calls whom in a push-pull round, and which calls are lost, does not
