@@ -26,8 +26,12 @@ Layers:
   csrc/gs_windows.cpp       host side of the unsharded flood: host- and device-driven windows
   csrc/gs_shards.cpp        host side of flood node-range shards and their exchanges
   csrc/gs_pushpull_host.cpp host side of push-pull: sparse rounds, shards, batched trials
-  csrc/gs_rumor_host.cpp    host side of rumor mongering: buffers, round loop, stop rule
-  csrc/gs_rumorset_host.cpp host side of a rumor set: refusals, buffers, round loop, per-rumor results
+  csrc/gs_rumor_host.cpp    host side of rumor mongering: buffers, its launchers for the round loop
+  csrc/gs_median_host.cpp   host side of median-counter push-pull: the same, and its batched trials
+  csrc/gs_rumorset_host.cpp host side of a rumor set: refusals, buffers, its launchers and row hook for
+                            the round loop, per-rumor results
+  csrc/gs_round_host.cpp    the round loop those three share: step, read-back, accounting, gs_run's stop rule
+  csrc/gs_trials_host.cpp   the step and run loops the batched-trial engines share
   csrc/gs_devmem.cpp        process-wide cache of large device blocks (gs_trim)
   csrc/gossip_sim.cpp       CLI with the reference's flags and stdout
   engine.py                 Python host API (ctypes)

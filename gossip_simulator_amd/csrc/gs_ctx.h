@@ -4,7 +4,8 @@
 // the flood engines, gs_pushpull_host.cpp push-pull, gs_rumor_host.cpp rumor
 // mongering, gs_median_host.cpp median-counter push-pull, gs_trials_host.cpp
 // the batched trials' shared loops, gs_rumorset_host.cpp concurrent push-pull
-// rumors, gs_api.cpp the entry points).
+// rumors, gs_round_host.cpp the shared round loop of those three one-trial
+// engines, gs_api.cpp the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -460,6 +461,42 @@ int trial_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_po
 int trial_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
               int32_t* status, const TrialLaunch& launch, uint64_t (*row_msgs)(const uint32_t* r));
 int trial_read_words(gs_ctx* c, uint64_t* words, const unsigned long long* d);
+
+// gs_round_host.cpp
+// What a one-trial, self-terminating engine gives the shared round loop: the
+// round's two halves (launches on c->stream for round tt; the commit half
+// holds whatever else the engine enqueues or flips per round), its control
+// block (device, pinned copy, and where the pinned copy keeps the three words
+// the loop reads), and for an engine that has them a second ring beside the
+// stats ring (`words` per slot; 0: none) and a hook run for every row read
+// back (the ring's slot, null without a ring, and whether the tick is a poll),
+// which then takes the trial's tick_99 itself.  name: as in "the <name>
+// control block ...".
+using RoundLaunch = std::function<int(uint32_t tt)>;
+struct RoundCtl {
+  const void* d;
+  void* h;
+  size_t bytes;
+  const unsigned long long *received, *pending;
+  const uint32_t* stop;
+};
+struct RoundRing {
+  const unsigned long long* d;
+  unsigned long long* h;
+  uint32_t words;
+};
+struct RoundEngine {
+  const char* name;
+  RoundLaunch round, commit;
+  RoundCtl ctl;
+  RoundRing ring;
+  std::function<void(uint64_t tick, const unsigned long long* slot, bool poll)> row;
+};
+int round_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls, const RoundEngine& e);
+int round_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
+              int32_t* status, const RoundEngine& e);
+uint32_t env_grid(const char* name);  // a GS_*_GRID variable clamped to 1..4096; 0: unset
+int read_words(gs_ctx* c, uint64_t* words, const unsigned long long* d);  // d's W words to the host, then the sync
 
 // gs_rumor_host.cpp
 int rumor_refuse(const gs_params* params, const char* what);

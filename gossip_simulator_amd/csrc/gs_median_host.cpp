@@ -1,8 +1,8 @@
 // gs_median_host.cpp -- the host side of median-counter push-pull
-// (GS_MODEL_MEDIAN): its buffers, the round loop and
-// gs_run's stop rule.  One trial on one device (the kernels are in
-// gs_median.hip), or a batch of trials, a workgroup each (gs_create_batch;
-// gs_median_trials.hip).
+// (GS_MODEL_MEDIAN): its buffers and what it gives the
+// shared round loop (gs_round_host.cpp: the step loop and gs_run's stop rule).
+// One trial on one device (the kernels are in gs_median.hip), or a batch of
+// trials, a workgroup each (gs_create_batch; gs_median_trials.hip).
 #include "gs_ctx.h"
 
 namespace gs {
@@ -15,19 +15,23 @@ MedianState median_state(const gs_ctx* c) {
                      (unsigned long long*)c->md.gotc.p, c->p.rumor_k};
 }
 
-// The round's counters on the host (rumor_account's rule): tick_99 is taken at
-// polls only.
-void median_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, bool poll, gs_tick_stats* o) {
-  c->t = tick;
-  c->fired += s[ST_FIRED];
-  c->sent += s[ST_SENT];
-  c->msgs += s[ST_MSGS];
-  c->recv += s[ST_RECV];
-  c->pending = s[ST_SCHED];  // the active nodes after the round
-  TrialAcc& a = c->tacc[0];
-  a.fired = c->fired; a.sent = c->sent; a.msgs = c->msgs; a.recv = c->recv;
-  if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = tick;
-  if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
+// What the shared round loop (gs_round_host.cpp) runs for this context; rlen
+// holds the active nodes after the round.
+RoundEngine median_engine(gs_ctx* c) {
+  const MedianState ms = median_state(c);
+  RumorCtl* h = c->md.h_ctl;
+  RoundEngine e{};
+  e.name = "median";
+  e.round = [c, ms](uint32_t tt) -> int {
+    CK(c, median_round(c->st, ms, tt, c->md.grid, c->stream));
+    return GS_OK;
+  };
+  e.commit = [c, ms](uint32_t tt) -> int {
+    CK(c, median_commit(c->st, ms, tt, c->stream));
+    return GS_OK;
+  };
+  e.ctl = RoundCtl{c->md.ctlb.p, h, sizeof(RumorCtl), &h->received, &h->rlen, &h->stop};
+  return e;
 }
 
 // ---- batched trials --------------------------------
@@ -275,9 +279,8 @@ int median_begin(gs_ctx* c, uint64_t sender) {
   CK(c, hipSetDevice(c->dev));
   // GS_MEDIAN_GRID: the round kernel's blocks (read per broadcast, so tests can
   // make a short table take several passes of the grid)
-  const char* e = getenv("GS_MEDIAN_GRID");
   MedianBufs& b = c->md;
-  b.grid = median_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
+  b.grid = median_grid(c->st.n, env_grid("GS_MEDIAN_GRID"));
   CK(c, hipMemsetAsync(b.ctlb.p, 0, sizeof(RumorCtl), c->stream));
   CK(c, hipMemsetAsync(b.st.p, 0, c->st.n, c->stream));
   CK(c, hipMemsetAsync(b.own.p, 0, c->st.n, c->stream));
@@ -292,84 +295,20 @@ int median_begin(gs_ctx* c, uint64_t sender) {
   return GS_OK;
 }
 
-// `ticks` rounds, enqueued without a host sync between them; the stats rows
-// and the control block come back once per call (per kStatSlots rounds).
-// every_tick_polls: each tick is a poll (gs_step returns every tick's row);
-// else only the call's last tick is (gs_run).
+// The rounds and the run on the shared loop (gs_round_host.cpp; a batch's on
+// gs_trials_host.cpp's).  The run stops at the first poll with no active node
+// (covered or quiescent by the float32 rule at that poll), or at max_ticks.
+// Reaching 99 % does not stop it.
 int median_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
   if (c->mdt) return trial_step(c, ticks, out, every_tick_polls, mdt_launch(c), mdt_row_msgs);
-  CK(c, hipSetDevice(c->dev));
-  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
-  const MedianState ms = median_state(c);
-  MedianBufs& b = c->md;
-  uint32_t done = 0;
-  while (done < ticks) {
-    const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
-    const uint64_t t0 = c->t + 1;
-    const StatSpans sp = stat_spans(t0, batch);
-    while (timing && c->ev.size() < (size_t)batch * 3) {
-      hipEvent_t ev;
-      CK(c, hipEventCreate(&ev));
-      c->ev.push_back(ev);
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const uint32_t tt = (uint32_t)(t0 + i);
-      hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
-      if (ev) CK(c, hipEventRecord(ev[0], c->stream));
-      CK(c, median_round(c->st, ms, tt, b.grid, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[1], c->stream));
-      CK(c, median_commit(c->st, ms, tt, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[2], c->stream));
-    }
-    for (int j = 0; j < sp.n; ++j)
-      CK(c, hipMemcpyAsync(c->h_stats + sp.off[j], c->st.stats + sp.off[j], sp.words[j] * 8, hipMemcpyDeviceToHost,
-                           c->stream));
-    CK(c, hipMemcpyAsync(b.h_ctl, b.ctlb.p, sizeof(RumorCtl), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < batch && timing; ++i) {
-      float ms_ = 0;
-      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3], c->ev[(size_t)i * 3 + 1]));
-      c->timing.deliver_ms += ms_;  // the round kernel
-      c->timing.deliver_launches++;
-      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3 + 1], c->ev[(size_t)i * 3 + 2]));
-      c->timing.resolve_ms += ms_;  // commit + publish
-      c->timing.resolve_launches++;
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const unsigned long long* s = c->h_stats + (size_t)((t0 + i) % kStatSlots) * kStatFields;
-      const bool poll = every_tick_polls || done + i + 1 == ticks;
-      median_account(c, t0 + i, s, poll, out ? &out[done + i] : nullptr);
-    }
-    if (b.h_ctl->received != c->recv || b.h_ctl->rlen != c->pending)
-      return fail(c, GS_EDEVICE, "the median control block and the stats rows disagree");
-    done += batch;
-  }
-  return GS_OK;
+  return round_step(c, ticks, out, every_tick_polls, median_engine(c));
 }
 
-// The run goes to its own end: it stops at the first poll with no active node
-// (the device's stop word: covered or quiescent by the float32 rule at that
-// poll), or at max_ticks.  Reaching 99 % does not stop it.
 int median_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
                int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
   if (c->mdt) return trial_run(c, poll, max_ticks, out, cap, nout, status, mdt_launch(c), mdt_row_msgs);
-  size_t k = 0;
-  int32_t st = GS_RUN_MAX_TICKS;
-  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
-  for (;;) {
-    RC(median_step(c, poll, nullptr, false));
-    if (out && k < cap)
-      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
-    ++k;
-    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
-    if (c->md.h_ctl->stop) { st = (int32_t)c->md.h_ctl->stop - 1; break; }
-    if (c->t >= max_ticks) break;
-  }
-  snap_trial(c, 0, st);
-  if (nout) *nout = k;
-  if (status) *status = st;
-  return GS_OK;
+  return round_run(c, poll, max_ticks, out, cap, nout, status, median_engine(c));
 }
 
 // removed = the D set, built from the state bytes.
@@ -381,9 +320,7 @@ int median_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
   unsigned long long* d = (unsigned long long*)c->md.done.p;
   if (c->begun) CK(c, median_done_set(c->st, median_state(c), d, c->stream));
   else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));  // (st is the last run's: nothing is informed)
-  CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return GS_OK;
+  return read_words(c, words, d);
 }
 
 int median_read_state(gs_ctx* c, uint8_t* st, size_t n) {

@@ -1,5 +1,6 @@
 // gs_rumor_host.cpp -- the host side of rumor mongering (GS_MODEL_RUMOR,
-// DESIGN.md section 4.7): its buffers, the round loop and gs_run's stop rule.
+// DESIGN.md section 4.7): its buffers and what it gives the shared round loop
+// (gs_round_host.cpp: the step loop and gs_run's stop rule).
 // One trial on one device (the kernels are in gs_rumor.hip), or a batch of
 // trials, a workgroup each (gs_create_trials; gs_rumor_trials.hip).
 #include "gs_ctx.h"
@@ -19,19 +20,30 @@ RumorState rumor_state(const gs_ctx* c) {
 
 bool pull(const gs_ctx* c) { return (c->p.rumor_mode & GS_RUMOR_PULL) != 0; }
 
-// The round's counters on the host: c's cumulative figures and its one
-// TrialAcc.  tick_99 is taken at polls only: `poll` says this tick is one.
-void rumor_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, bool poll, gs_tick_stats* o) {
-  c->t = tick;
-  c->fired += s[ST_FIRED];
-  c->sent += s[ST_SENT];
-  c->msgs += s[ST_MSGS];
-  c->recv += s[ST_RECV];
-  c->pending = s[ST_SCHED];  // the hot nodes after the round
-  TrialAcc& a = c->tacc[0];
-  a.fired = c->fired; a.sent = c->sent; a.msgs = c->msgs; a.recv = c->recv;
-  if (poll && !a.tick99 && covered(a.recv, c->p.n)) a.tick99 = tick;
-  if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
+// What the shared round loop (gs_round_host.cpp) runs for this context: the
+// dense round of the pull modes, or the list round, which swaps the two lists
+// after its commit.
+RoundEngine rumor_engine(gs_ctx* c) {
+  const RumorState rs = rumor_state(c);
+  const bool dense = pull(c);
+  RumorCtl* h = c->rm.h_ctl;
+  RoundEngine e{};
+  e.name = "rumor";
+  e.round = [c, rs, dense](uint32_t tt) -> int {
+    if (dense)
+      CK(c, rumor_pull_round(c->st, rs, tt, c->rm.grid, c->stream));
+    else
+      CK(c, rumor_round(c->st, rs, (const uint32_t*)c->rm.list[c->rm.cur].p, (uint32_t*)c->rm.list[c->rm.cur ^ 1].p,
+                        tt, c->rm.grid, c->stream));
+    return GS_OK;
+  };
+  e.commit = [c, rs, dense](uint32_t tt) -> int {
+    CK(c, dense ? rumor_pull_commit(c->st, rs, tt, c->stream) : rumor_commit(c->st, rs, tt, c->stream));
+    c->rm.cur ^= 1;
+    return GS_OK;
+  };
+  e.ctl = RoundCtl{c->rm.ctlb.p, h, sizeof(RumorCtl), &h->received, &h->rlen, &h->stop};
+  return e;
 }
 
 // ---- batched trials --------------------------------
@@ -196,8 +208,7 @@ int rumor_begin(gs_ctx* c, uint64_t sender) {
   CK(c, hipSetDevice(c->dev));
   // GS_RUMOR_GRID: the round kernel's blocks (read per broadcast, so tests can
   // make a short list take several passes of the grid)
-  const char* e = getenv("GS_RUMOR_GRID");
-  c->rm.grid = rumor_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
+  c->rm.grid = rumor_grid(c->st.n, env_grid("GS_RUMOR_GRID"));
   c->rm.cur = 0;
   CK(c, hipMemsetAsync(c->rm.ctlb.p, 0, sizeof(RumorCtl), c->stream));
   CK(c, hipMemsetAsync(c->rm.miss.p, 0, c->st.n, c->stream));
@@ -216,89 +227,20 @@ int rumor_begin(gs_ctx* c, uint64_t sender) {
   return GS_OK;
 }
 
-// `ticks` rounds, enqueued without a host sync between them; the stats rows
-// and the control block come back once per call (per kStatSlots rounds).
-// every_tick_polls: each tick is a poll (gs_step returns every tick's row);
-// else only the call's last tick is (gs_run).
+// The rounds and the run on the shared loop (gs_round_host.cpp; a batch's on
+// gs_trials_host.cpp's).  The run stops at the first poll with no hot node
+// (covered or quiescent by the float32 rule at that poll), or at max_ticks.
+// Reaching 99 % does not stop it.
 int rumor_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
   if (c->rmt) return trial_step(c, ticks, out, every_tick_polls, rmt_launch(c), rmt_row_msgs);
-  CK(c, hipSetDevice(c->dev));
-  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
-  const RumorState rs = rumor_state(c);
-  const bool dense = pull(c);
-  uint32_t done = 0;
-  while (done < ticks) {
-    const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
-    const uint64_t t0 = c->t + 1;
-    const StatSpans sp = stat_spans(t0, batch);
-    while (timing && c->ev.size() < (size_t)batch * 3) {
-      hipEvent_t ev;
-      CK(c, hipEventCreate(&ev));
-      c->ev.push_back(ev);
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const uint32_t tt = (uint32_t)(t0 + i);
-      hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
-      if (ev) CK(c, hipEventRecord(ev[0], c->stream));
-      if (dense)
-        CK(c, rumor_pull_round(c->st, rs, tt, c->rm.grid, c->stream));
-      else
-        CK(c, rumor_round(c->st, rs, (const uint32_t*)c->rm.list[c->rm.cur].p, (uint32_t*)c->rm.list[c->rm.cur ^ 1].p,
-                          tt, c->rm.grid, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[1], c->stream));
-      CK(c, dense ? rumor_pull_commit(c->st, rs, tt, c->stream) : rumor_commit(c->st, rs, tt, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[2], c->stream));
-      c->rm.cur ^= 1;
-    }
-    for (int j = 0; j < sp.n; ++j)
-      CK(c, hipMemcpyAsync(c->h_stats + sp.off[j], c->st.stats + sp.off[j], sp.words[j] * 8, hipMemcpyDeviceToHost,
-                           c->stream));
-    CK(c, hipMemcpyAsync(c->rm.h_ctl, c->rm.ctlb.p, sizeof(RumorCtl), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < batch && timing; ++i) {
-      float ms = 0;
-      CK(c, hipEventElapsedTime(&ms, c->ev[(size_t)i * 3], c->ev[(size_t)i * 3 + 1]));
-      c->timing.deliver_ms += ms;  // the round kernel
-      c->timing.deliver_launches++;
-      CK(c, hipEventElapsedTime(&ms, c->ev[(size_t)i * 3 + 1], c->ev[(size_t)i * 3 + 2]));
-      c->timing.resolve_ms += ms;  // commit + publish
-      c->timing.resolve_launches++;
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const unsigned long long* s = c->h_stats + (size_t)((t0 + i) % kStatSlots) * kStatFields;
-      const bool poll = every_tick_polls || done + i + 1 == ticks;
-      rumor_account(c, t0 + i, s, poll, out ? &out[done + i] : nullptr);
-    }
-    if (c->rm.h_ctl->received != c->recv || c->rm.h_ctl->rlen != c->pending)
-      return fail(c, GS_EDEVICE, "the rumor control block and the stats rows disagree");
-    done += batch;
-  }
-  return GS_OK;
+  return round_step(c, ticks, out, every_tick_polls, rumor_engine(c));
 }
 
-// The run goes to its own end: it stops at the first poll with no hot node
-// (the device's stop word: covered or quiescent by the float32 rule at that
-// poll), or at max_ticks.  Reaching 99 % does not stop it.
 int rumor_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
               int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin first");
   if (c->rmt) return trial_run(c, poll, max_ticks, out, cap, nout, status, rmt_launch(c), rmt_row_msgs);
-  size_t k = 0;
-  int32_t st = GS_RUN_MAX_TICKS;
-  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
-  for (;;) {
-    RC(rumor_step(c, poll, nullptr, false));
-    if (out && k < cap)
-      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
-    ++k;
-    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
-    if (c->rm.h_ctl->stop) { st = (int32_t)c->rm.h_ctl->stop - 1; break; }
-    if (c->t >= max_ticks) break;
-  }
-  snap_trial(c, 0, st);
-  if (nout) *nout = k;
-  if (status) *status = st;
-  return GS_OK;
+  return round_run(c, poll, max_ticks, out, cap, nout, status, rumor_engine(c));
 }
 
 // removed = informed and not hot: a copy of recv less the current list's nodes
@@ -317,9 +259,7 @@ int rumor_read_removed(gs_ctx* c, uint64_t* words, size_t nwords) {
     if (c->begun)  // (before a broadcast recv is empty and the list is the last run's)
       CK(c, rumor_removed(rumor_state(c), (const uint32_t*)c->rm.list[c->rm.cur].p, d, c->rm.grid, c->stream));
   }
-  CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return GS_OK;
+  return read_words(c, words, d);
 }
 
 }  // namespace gs

@@ -1,7 +1,8 @@
 // gs_rumorset_host.cpp -- the host side of concurrent push-pull rumors
 // (gs_create_rumorset): the create's refusals, the
-// buffers, the round loop, gs_run's stop rule and the per-rumor results.  One
-// device; the kernels are in gs_rumorset.hip.
+// buffers, what it gives the shared round loop (gs_round_host.cpp: the step
+// loop and gs_run's stop rule) and the per-rumor results.  One device; the
+// kernels are in gs_rumorset.hip and gs_rumorset_cap.hip.
 #include "gs_ctx.h"
 
 namespace gs {
@@ -13,26 +14,43 @@ RsState rs_state(const gs_ctx* c) {
                  (unsigned long long*)c->rsb.own.p, (unsigned long long*)c->rsb.ring.p, c->rumors};
 }
 
-// One round's row and counts on the host.  Rumor j's tick_99 and the set's
-// (the first poll with no started rumor uncovered) are taken at polls only
-// (median_account's rule).
-void rs_account(gs_ctx* c, uint64_t tick, const unsigned long long* s, const unsigned long long* counts, bool poll,
-                gs_tick_stats* o) {
+// What the shared round loop (gs_round_host.cpp) runs for this context.  A
+// capped set's round kernel is gs_rumorset_cap.hip's; the commit half first
+// injects the live rumors that enter after this round's commit (the host
+// knows the starts).  The count ring comes back beside the stats rows, and a
+// row's hook takes its counts: rumor j's tick_99 and the set's (the first poll
+// with no started rumor uncovered) are taken at polls only.
+RoundEngine rs_engine(gs_ctx* c) {
+  const RsState rs = rs_state(c);
   RsBufs& b = c->rsb;
-  c->t = tick;
-  c->fired += s[ST_FIRED];
-  c->sent += s[ST_SENT];
-  c->msgs += s[ST_MSGS];
-  c->recv += s[ST_RECV];
-  c->pending = s[ST_SCHED];
-  for (uint32_t j = 0; j < c->rumors; ++j) {
-    b.count[j] = counts[j];
-    if (poll && ((b.live >> j) & 1) && !b.tick99[j] && covered(b.count[j], c->p.n)) b.tick99[j] = tick;
-  }
-  TrialAcc& a = c->tacc[0];
-  a.fired = c->fired; a.sent = c->sent; a.msgs = c->msgs; a.recv = c->recv;
-  if (poll && !a.tick99 && b.live && c->pending == 0) a.tick99 = tick;
-  if (o) *o = gs_tick_stats{c->t, s[ST_FIRED], s[ST_SENT], s[ST_MSGS], c->recv, 0, c->pending};
+  RoundEngine e{};
+  e.name = "rumor set's";
+  e.round = [c, rs, &b](uint32_t tt) -> int {
+    if (b.payload) CK(c, rsc_round(c->st, rs, tt, b.payload, b.pick, b.grid, c->stream));
+    else CK(c, rs_round(c->st, rs, tt, b.grid, c->stream));
+    return GS_OK;
+  };
+  e.commit = [c, rs, &b](uint32_t tt) -> int {
+    if (tt <= b.last_start) {
+      unsigned long long in = 0;
+      for (uint32_t j = 0; j < c->rumors; ++j)
+        if (b.start[j] == tt) in |= 1ull << j;
+      if (in & b.live) CK(c, rsc_inject(rs, b.snd, in & b.live, c->stream));
+    }
+    CK(c, rs_commit(c->st, rs, tt, b.grid, c->stream));
+    return GS_OK;
+  };
+  e.ctl = RoundCtl{b.ctlb.p, b.h_ctl, sizeof(RsCtl), &b.h_ctl->received, &b.h_ctl->pending, &b.h_ctl->stop};
+  e.ring = RoundRing{rs.ring, b.h_ring, kRsMax};
+  e.row = [c, &b](uint64_t tick, const unsigned long long* counts, bool poll) {
+    for (uint32_t j = 0; j < c->rumors; ++j) {
+      b.count[j] = counts[j];
+      if (poll && ((b.live >> j) & 1) && !b.tick99[j] && covered(b.count[j], c->p.n)) b.tick99[j] = tick;
+    }
+    TrialAcc& a = c->tacc[0];
+    if (poll && !a.tick99 && b.live && c->pending == 0) a.tick99 = tick;
+  };
+  return e;
 }
 
 }  // namespace
@@ -89,9 +107,8 @@ int rs_begin(gs_ctx* c, const int64_t* senders, const int64_t* starts) {
   CK(c, hipSetDevice(c->dev));
   // GS_RUMORSET_GRID: the blocks of the round and the commit (read per
   // broadcast, so tests can make a short table take several passes of the grid)
-  const char* e = getenv("GS_RUMORSET_GRID");
   RsBufs& b = c->rsb;
-  b.grid = rs_grid(c->st.n, e ? (uint32_t)std::min(std::max(atoi(e), 1), 4096) : 0u);
+  b.grid = rs_grid(c->st.n, env_grid("GS_RUMORSET_GRID"));
   b.snd = RsSenders{};
   b.last_start = 0;
   unsigned long long now = 0;
@@ -152,95 +169,20 @@ int rs_traffic(gs_ctx* c, gs_rumorset_traffic* out) {
   return GS_OK;
 }
 
-// `ticks` rounds, three launches each (a capped set's round kernel is
-// gs_rumorset_cap.hip's; one more launch in a round after which a late rumor
-// enters), enqueued without a host sync between them; the stats rows, the count ring's slots and the control block come back
-// once per call (per kStatSlots rounds).  every_tick_polls: each tick is a
-// poll (gs_step); else only the call's last tick is (gs_run).
+// The rounds and the run on the shared loop (gs_round_host.cpp): three
+// launches a round, one more in a round after which a late rumor enters.  The
+// run stops at the first poll with no started rumor below 99 % (the device's
+// stop word: covered, or quiescent if no rumor started), or at max_ticks.
+// There is no test for "nothing can change": a masked run that cannot reach
+// 99 % ends at max_ticks.
 int rs_step(gs_ctx* c, uint32_t ticks, gs_tick_stats* out, bool every_tick_polls) {
-  CK(c, hipSetDevice(c->dev));
-  const bool timing = (c->p.flags & GS_FLAG_TIMING) != 0;
-  const RsState rs = rs_state(c);
-  RsBufs& b = c->rsb;
-  uint32_t done = 0;
-  while (done < ticks) {
-    const uint32_t batch = std::min<uint32_t>(ticks - done, timing ? 256u : kStatSlots);
-    const uint64_t t0 = c->t + 1;
-    const StatSpans sp = stat_spans(t0, batch);
-    while (timing && c->ev.size() < (size_t)batch * 3) {
-      hipEvent_t ev;
-      CK(c, hipEventCreate(&ev));
-      c->ev.push_back(ev);
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const uint32_t tt = (uint32_t)(t0 + i);
-      hipEvent_t* ev = timing ? &c->ev[(size_t)i * 3] : nullptr;
-      if (ev) CK(c, hipEventRecord(ev[0], c->stream));
-      if (b.payload) CK(c, rsc_round(c->st, rs, tt, b.payload, b.pick, b.grid, c->stream));
-      else CK(c, rs_round(c->st, rs, tt, b.grid, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[1], c->stream));
-      if (tt <= b.last_start) {  // the live rumors that enter after this round's commit (the host knows the starts)
-        unsigned long long in = 0;
-        for (uint32_t j = 0; j < c->rumors; ++j)
-          if (b.start[j] == tt) in |= 1ull << j;
-        if (in & b.live) CK(c, rsc_inject(rs, b.snd, in & b.live, c->stream));
-      }
-      CK(c, rs_commit(c->st, rs, tt, b.grid, c->stream));
-      if (ev) CK(c, hipEventRecord(ev[2], c->stream));
-    }
-    for (int j = 0; j < sp.n; ++j) {  // a ring slot is kRsMax words where a stats row is kStatFields
-      const size_t off = sp.off[j] / kStatFields * kRsMax, words = sp.words[j] / kStatFields * kRsMax;
-      CK(c, hipMemcpyAsync(c->h_stats + sp.off[j], c->st.stats + sp.off[j], sp.words[j] * 8, hipMemcpyDeviceToHost,
-                           c->stream));
-      CK(c, hipMemcpyAsync(b.h_ring + off, rs.ring + off, words * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    CK(c, hipMemcpyAsync(b.h_ctl, b.ctlb.p, sizeof(RsCtl), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < batch && timing; ++i) {
-      float ms_ = 0;
-      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3], c->ev[(size_t)i * 3 + 1]));
-      c->timing.deliver_ms += ms_;  // the round kernel
-      c->timing.deliver_launches++;
-      CK(c, hipEventElapsedTime(&ms_, c->ev[(size_t)i * 3 + 1], c->ev[(size_t)i * 3 + 2]));
-      c->timing.resolve_ms += ms_;  // commit + publish
-      c->timing.resolve_launches++;
-    }
-    for (uint32_t i = 0; i < batch; ++i) {
-      const size_t slot = (size_t)((t0 + i) % kStatSlots);
-      const bool poll = every_tick_polls || done + i + 1 == ticks;
-      rs_account(c, t0 + i, c->h_stats + slot * kStatFields, b.h_ring + slot * kRsMax, poll,
-                 out ? &out[done + i] : nullptr);
-    }
-    if (b.h_ctl->received != c->recv || b.h_ctl->pending != c->pending)
-      return fail(c, GS_EDEVICE, "the rumor set's control block and the stats rows disagree");
-    done += batch;
-  }
-  return GS_OK;
+  return round_step(c, ticks, out, every_tick_polls, rs_engine(c));
 }
 
-// Stops at the first poll with no started rumor below 99 % (the device's stop
-// word: covered, or quiescent if no rumor started), or at max_ticks.  There
-// is no test for "nothing can change": a masked run that cannot reach 99 %
-// ends at max_ticks.
 int rs_run(gs_ctx* c, uint32_t poll, uint64_t max_ticks, gs_tick_stats* out, size_t cap, size_t* nout,
            int32_t* status) {
   if (!c->begun) return fail(c, GS_EINVAL, "gs_broadcast_begin or gs_rumorset_begin first");
-  size_t k = 0;
-  int32_t st = GS_RUN_MAX_TICKS;
-  uint64_t f0 = c->fired, s0 = c->sent, m0 = c->msgs;
-  for (;;) {
-    RC(rs_step(c, poll, nullptr, false));
-    if (out && k < cap)
-      out[k] = gs_tick_stats{c->t, c->fired - f0, c->sent - s0, c->msgs - m0, c->recv, 0, c->pending};
-    ++k;
-    f0 = c->fired; s0 = c->sent; m0 = c->msgs;
-    if (c->rsb.h_ctl->stop) { st = (int32_t)c->rsb.h_ctl->stop - 1; break; }
-    if (c->t >= max_ticks) break;
-  }
-  snap_trial(c, 0, st);
-  if (nout) *nout = k;
-  if (status) *status = st;
-  return GS_OK;
+  return round_run(c, poll, max_ticks, out, cap, nout, status, rs_engine(c));
 }
 
 int rs_results(gs_ctx* c, gs_rumor_stats* out, size_t cap, size_t* nout) {
@@ -276,9 +218,7 @@ int rs_read_column(gs_ctx* c, uint32_t rumor, uint64_t* words, size_t nwords) {
   unsigned long long* d = (unsigned long long*)c->rsb.col.p;
   if (c->begun) CK(c, rs_column(c->st, rs_state(c), rumor, d, c->stream));
   else CK(c, hipMemsetAsync(d, 0, c->st.W * 8, c->stream));
-  CK(c, hipMemcpyAsync(words, d, c->st.W * 8, hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return GS_OK;
+  return read_words(c, words, d);
 }
 
 }  // namespace gs

@@ -2,7 +2,8 @@
 // (batched push-pull, rumor and median trials): what a
 // device grants their rounds kernels, and the step and run loops over the
 // per-trial counter rows.  An engine supplies its launcher and how a row
-// yields its messages (gs_rumor_host.cpp, gs_median_host.cpp).
+// yields its messages (gs_rumor_host.cpp, gs_median_host.cpp).  The one-trial
+// rumor, median and rumor-set engines have their loop in gs_round_host.cpp.
 #include "gs_ctx.h"
 
 namespace gs {
