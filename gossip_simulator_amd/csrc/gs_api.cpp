@@ -909,10 +909,14 @@ int gs_set_trial(gs_ctx* c, uint32_t trial) {
       RC(gs_set_trial(m, c->gtrials ? t : trial) ? fail(c, GS_EINVAL, m->err) : 0);
       t += m->trials;
     }
+    // push-pull shards: the replicas run the sparse early rounds under the same key
+    for (gs_ctx* r : c->gr.reps)
+      if (r) r->p.trial = r->st.key.trial = trial;
     c->p.trial = trial;
     c->peers = false;
     return GS_OK;
   }
+  if (c->rs.rep && c->rs.own_rep) c->rs.rep->p.trial = c->rs.rep->st.key.trial = trial;  // (a rank's own replica)
   c->p.trial = trial;
   c->st.key.trial = trial;
   c->ws.key.trial = trial;

@@ -19,6 +19,13 @@
 #include <mutex>
 #include <vector>
 
+// The fill of GS_DEVMEM_POISON is the only use of hipMemset here, and only
+// with the switch on.  The reference is weak so that a program that links this
+// file against driver entry points of its own (tests/devmem_harness.cpp) needs
+// the eighth one only if it turns the switch on; in the library it binds to
+// the runtime's like every other call.
+#pragma weak hipMemset
+
 namespace {
 
 constexpr size_t kCacheMin = 64ull << 20;  // smaller blocks: plain hipMalloc / hipFree
@@ -64,6 +71,20 @@ bool enabled() {
     return !(s && atoi(s) == 0);
   }();
   return on;
+}
+
+// GS_DEVMEM_POISON=<byte> (decimal or 0x.., 1..255): every block handed out
+// is filled with that byte first, so that a read of bytes nobody wrote shows
+// the same wrong value in every process.  0: off.
+int poison() {
+  static const int v = [] {
+    const char* s = getenv("GS_DEVMEM_POISON");
+    if (!s || !*s) return 0;
+    char* end = nullptr;
+    const long x = strtol(s, &end, 0);
+    return (*end || x < 1 || x > 255) ? 0 : (int)x;
+  }();
+  return v;
 }
 
 double now_ms() {
@@ -168,18 +189,23 @@ char* take_cached(Cache& c, int dev, size_t need, bool picky) {
 }
 }  // namespace
 
-hipError_t gs_dev_malloc(void** p, size_t bytes) {
-  if (!p) return hipErrorInvalidValue;
+namespace {
+// the block and its whole size (a cached block: rounded up to kGran); *hit: it
+// was counted as a cache hit
+hipError_t alloc_block(void** p, size_t bytes, size_t* size, bool* hit) {
   Cache& c = cache();
+  *size = bytes;
   if (!enabled() || bytes < kCacheMin) return timed_malloc(c, p, bytes);
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   const size_t need = (bytes + kGran - 1) & ~(kGran - 1);
+  *size = need;
   {
     std::lock_guard<std::mutex> g(c.mu);
     if (char* b = take_cached(c, dev, need, true)) {
       *p = b;
+      *hit = true;
       return hipSuccess;
     }
   }
@@ -206,6 +232,7 @@ hipError_t gs_dev_malloc(void** p, size_t bytes) {
       std::lock_guard<std::mutex> g(c.mu);
       if (char* b = take_cached(c, dev, need, false)) {
         *p = b;
+        *hit = true;
         return hipSuccess;
       }
       t = collect_trim(c, dev);
@@ -218,6 +245,7 @@ hipError_t gs_dev_malloc(void** p, size_t bytes) {
       std::lock_guard<std::mutex> g(c.mu);
       if (char* b = take_cached(c, dev, need, false)) {  // (another thread freed one meanwhile)
         *p = b;
+        *hit = true;
         return hipSuccess;
       }
       return e;
@@ -229,6 +257,32 @@ hipError_t gs_dev_malloc(void** p, size_t bytes) {
   c.st.mapped_bytes += need;
   *p = q;
   return hipSuccess;
+}
+}  // namespace
+
+hipError_t gs_dev_malloc(void** p, size_t bytes) {
+  if (!p) return hipErrorInvalidValue;
+  size_t size = 0;
+  bool hit = false;
+  hipError_t e = alloc_block(p, bytes, &size, &hit);
+  const int v = poison();
+  if (e != hipSuccess || !v) return e;
+  static std::once_flag said;
+  std::call_once(said, [v] { fprintf(stderr, "[devmem] poison 0x%02X\n", v); });
+  e = &hipMemset ? hipMemset(*p, v, size) : hipErrorNotSupported;
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) return e;
+  // a failed fill hands out nothing: the block goes back as a free would put
+  // it (a slab mapped for it stays cached), and was no hit
+  (void)hipGetLastError();
+  (void)gs_dev_free(*p);
+  *p = nullptr;
+  if (hit) {
+    Cache& c = cache();
+    std::lock_guard<std::mutex> g(c.mu);
+    --c.st.cache_hits;
+  }
+  return e;
 }
 
 namespace {

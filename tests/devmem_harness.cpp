@@ -2,7 +2,7 @@
 // reverse-table pass planner (gs_rev_plan.h) against plain models, on the CPU.
 //
 // This program is linked with the product's gs_devmem.cpp, unchanged, and
-// defines the seven HIP entry points that file calls itself: a fake driver
+// defines the eight HIP entry points that file calls itself: a fake driver
 // with several devices, a capacity per device, a table of live allocations and
 // a log of every call.  Nothing backs the addresses it hands out; they come
 // from a high range and are never reused, so a stale address cannot alias a
@@ -10,8 +10,8 @@
 //
 //   devmem_harness <scenario>      one JSON line; exit status 1 on a violated check
 //
-// The process reads GS_DEVMEM_CACHE once, so every scenario is a fresh process
-// (tests/test_devmem_model.py).
+// The process reads GS_DEVMEM_CACHE and GS_DEVMEM_POISON once, so every
+// scenario is a fresh process (tests/test_devmem_model.py).
 //
 // The model (struct Sim) is written from the contract in gs_devmem.h and the
 // header comment of gs_devmem.cpp, not from the allocator's code: a flat list
@@ -67,11 +67,12 @@ std::string g_scenario, g_ctx;
 
 // ---------------------------------------------------------------- fake driver
 struct Call {
-  char kind;  // M hipMalloc, F hipFree, Y hipDeviceSynchronize, S hipSetDevice, I hipMemGetInfo
+  char kind;  // M hipMalloc, F hipFree, Y hipDeviceSynchronize, S hipSetDevice, I hipMemGetInfo, Z hipMemset
   int dev;    // the calling thread's current device (S: the new one)
   uintptr_t addr;
   size_t size;
   hipError_t err;
+  int value = 0;  // Z: the byte
 };
 struct Alloc {
   size_t size;
@@ -87,6 +88,7 @@ struct Fake {
   uintptr_t next = 0x700000000000ull;
   bool contiguous = false;  // place the next allocations back to back
   int fail_next = 0;        // fail that many hipMallocs whatever the room (fragmentation)
+  int fail_fill = 0;        // fail that many hipMemsets
   uint64_t n_malloc = 0, n_free = 0, unknown_free = 0, freed_under_block = 0;
   Fake() {
     for (size_t& c : capacity) c = kDeviceBytes;
@@ -165,6 +167,15 @@ hipError_t hipDeviceSynchronize(void) {
   f.log.push_back({'Y', t_dev, 0, 0, hipSuccess});
   return hipSuccess;
 }
+hipError_t hipMemset(void* p, int value, size_t size) {
+  Fake& f = fk();
+  std::lock_guard<std::mutex> g(f.mu);
+  const bool injected = f.fail_fill > 0;
+  if (injected) --f.fail_fill;
+  const hipError_t e = injected ? hipErrorLaunchFailure : hipSuccess;
+  f.log.push_back({'Z', t_dev, (uintptr_t)p, size, e, value});
+  return e;
+}
 hipError_t hipGetLastError(void) { return hipSuccess; }
 }
 
@@ -175,6 +186,15 @@ bool cache_enabled() {
   return !(s && atoi(s) == 0);
 }
 size_t round_up(size_t b) { return (b + kGran - 1) / kGran * kGran; }
+// GS_DEVMEM_POISON as DESIGN.md section 9.1 documents it: decimal or 0x.., 1..255, else off
+// (the out-of-range and malformed values are pinned from outside, by tests/test_devmem_model.py)
+int poison_byte() {
+  const char* s = getenv("GS_DEVMEM_POISON");
+  if (!s || !*s) return 0;
+  char* end = nullptr;
+  const long v = strtol(s, &end, 0);
+  return (*end || v < 1 || v > 255) ? 0 : (int)v;
+}
 
 // ------------------------------------------------------------------ the model
 enum Cls { PLAIN, PLAIN_FAIL, HIT, NEW_SLAB, FAIL };
@@ -216,6 +236,7 @@ struct Block {
 
 struct Sim {
   const bool enabled = cache_enabled();
+  const int poison = poison_byte();
   std::vector<MSlab> slabs;
   std::vector<Block> blocks;  // live, handed out
   uint64_t hits = 0;
@@ -340,7 +361,7 @@ struct Sim {
   // ---- applying what the allocator did
   struct LogView {
     int mallocs = 0, syncs = 0;
-    std::vector<Call> frees, ok_mallocs, all_mallocs, sync_calls;
+    std::vector<Call> frees, ok_mallocs, all_mallocs, sync_calls, fills, all;
   };
   static LogView since(size_t mark) {
     Fake& f = fk();
@@ -348,6 +369,8 @@ struct Sim {
     LogView v;
     for (size_t i = mark; i < f.log.size(); ++i) {
       const Call& c = f.log[i];
+      v.all.push_back(c);
+      if (c.kind == 'Z') v.fills.push_back(c);
       if (c.kind == 'M') {
         ++v.mallocs;
         v.all_mallocs.push_back(c);
@@ -406,6 +429,21 @@ struct Sim {
     const bool cached = enabled && bytes >= kMin;
     for (const Call& c : v.all_mallocs) CHECK(c.size == (cached ? need : bytes) && c.dev == d, "hipMalloc size/device");
     apply_trims(v.frees, d, o.trimmed);
+    // the poison switch: off, the driver sees no fill; on, a block handed out
+    // was filled whole with the byte and the device synchronised, as the last
+    // two driver calls of the request
+    if (!poison || o.err != hipSuccess) {
+      CHECK(v.fills.empty(), "%zu fill(s) %s", v.fills.size(), poison ? "of a failed request" : "with the switch off");
+    } else {
+      CHECK(v.fills.size() == 1, "%zu fills of one block", v.fills.size());
+      const Call& z = v.fills[0];
+      CHECK(z.addr == o.addr && z.size == (cached ? need : bytes) && z.value == poison && z.dev == d,
+            "fill of %zu bytes at %#zx with %d", z.size, (size_t)z.addr, z.value);
+      const size_t k = v.all.size();
+      CHECK(k >= 2 && v.all[k - 2].kind == 'Z' && v.all[k - 1].kind == 'Y' && v.all[k - 1].dev == d,
+            "the fill and one sync do not end the request");
+      CHECK(v.syncs == 1, "%d syncs after one fill", v.syncs);
+    }
     switch (o.cls) {
       case PLAIN:
         CHECK(o.err == hipSuccess && v.ok_mallocs.size() == 1 && v.ok_mallocs[0].addr == o.addr);
@@ -450,6 +488,46 @@ struct Sim {
     if (!o.trimmed.empty()) key += "_after_trim";
     ++seen[key];
     check_all();
+    return o;
+  }
+
+  // a request whose fill fails: the fill's error, no block, and the books as
+  // they were -- but for a slab mapped for it, which stays cached
+  Outcome malloc_fill_fails(size_t bytes) {
+    CHECK(poison, "this needs GS_DEVMEM_POISON");
+    const int d = cur;
+    Outcome o = predict_malloc(d, bytes);
+    CHECK(o.cls == PLAIN || o.cls == HIT || o.cls == NEW_SLAB);
+    DevMemStats a, b;
+    gs_devmem_stats(&a);
+    size_t live_before;
+    {
+      std::lock_guard<std::mutex> g(fk().mu);
+      live_before = fk().live.size();
+      fk().fail_fill = 1;
+    }
+    const size_t m = mark();
+    void* p = (void*)16;
+    o.err = gs_dev_malloc(&p, bytes);
+    const LogView v = since(m);
+    CHECK(o.err == hipErrorLaunchFailure && !p, "a failed fill returned %d and %p", (int)o.err, p);
+    CHECK(v.fills.size() == 1 && v.fills[0].err != hipSuccess && v.mallocs == o.mallocs);
+    gs_devmem_stats(&b);
+    CHECK(b.hip_allocs == a.hip_allocs + (uint64_t)o.mallocs && b.cache_hits == a.cache_hits);
+    const size_t need = round_up(bytes);
+    if (o.cls == PLAIN) {  // the block went back to the driver
+      CHECK(v.frees.size() == 1 && v.frees[0].addr == v.ok_mallocs[0].addr && v.frees[0].err == hipSuccess);
+      CHECK(b.cached_bytes == a.cached_bytes && b.mapped_bytes == a.mapped_bytes);
+    } else if (o.cls == HIT) {  // the extent is free again and merged as before
+      CHECK(v.frees.empty() && b.cached_bytes == a.cached_bytes && b.mapped_bytes == a.mapped_bytes);
+    } else {  // the new slab is a free cached extent
+      CHECK(v.frees.empty() && v.ok_mallocs.size() == 1);
+      CHECK(b.mapped_bytes == a.mapped_bytes + need && b.cached_bytes == a.cached_bytes + need);
+      const uintptr_t base = v.ok_mallocs[0].addr;
+      slabs.push_back({base, need, d, {{base, need, false}}});
+    }
+    std::lock_guard<std::mutex> g(fk().mu);
+    CHECK(fk().live.size() == live_before + (o.cls == NEW_SLAB));
     return o;
   }
 
@@ -1050,6 +1128,86 @@ void split_coalesce() {
   ok(report(s));
 }
 
+// the poison switch on: every kind of successful request is filled (checked
+// in Sim::malloc), and a failed fill hands out nothing
+void poison_on() {  // run with GS_DEVMEM_POISON set
+  Sim s;
+  CHECK(s.poison, "this scenario needs GS_DEVMEM_POISON");
+  g_ctx = "plain";
+  Outcome o = s.malloc(MiB);
+  CHECK(o.cls == PLAIN);
+  o = s.malloc(kMin - 1);
+  CHECK(o.cls == PLAIN);
+  g_ctx = "new slab";
+  o = s.malloc(GiB + 1);  // rounded up: the fill covers the whole extent
+  CHECK(o.cls == NEW_SLAB);
+  const uintptr_t slab = o.addr;
+  s.free(slab);
+  g_ctx = "hit after a split";
+  o = s.malloc(256 * MiB);
+  CHECK(o.cls == HIT && o.ext_size == GiB + kGran && o.addr == slab);
+  o = s.malloc(128 * MiB + 5);
+  CHECK(o.cls == HIT && o.addr == slab + 256 * MiB);
+  o = s.malloc(640 * MiB);  // the rest, whole
+  CHECK(o.cls == HIT && o.ext_size == 640 * MiB);
+  g_ctx = "fallback after a failed hipMalloc";
+  uintptr_t t = s.malloc(8 * GiB).addr;
+  s.free(t);
+  o = s.malloc(2 * GiB);
+  CHECK(o.cls == HIT && o.addr == t);
+  s.set_room(0, 0);
+  o = s.malloc(64 * MiB);  // hipMalloc fails for lack of room: the relaxed fit
+  CHECK(o.cls == HIT && o.relaxed && o.mallocs == 1 && o.addr == t + 2 * GiB);
+  s.set_room(0, 64 * GiB);
+  while (!s.blocks.empty()) s.free(s.blocks.back().addr);
+  fk().fail_next = 1;
+  o = s.malloc(9 * GiB);  // the driver refuses once: every free slab back, then a new slab
+  CHECK(o.cls == NEW_SLAB && o.mallocs == 2 && o.trimmed == sizes({GiB + kGran, 8 * GiB}));
+  s.free(o.addr);
+  g_ctx = "failed fill: plain";
+  o = s.malloc_fill_fails(MiB);
+  CHECK(o.cls == PLAIN);
+  s.check_all();
+  g_ctx = "failed fill: hit";
+  o = s.malloc_fill_fails(3 * GiB);
+  CHECK(o.cls == HIT && o.ext_size == 9 * GiB);
+  s.check_all();
+  o = s.malloc(9 * GiB);  // the extent was put back whole
+  CHECK(o.cls == HIT && o.ext_size == 9 * GiB);
+  s.free(o.addr);
+  g_ctx = "failed fill: new slab";
+  o = s.malloc_fill_fails(64 * MiB);  // 9 GiB free is far too big for it: a slab of its own
+  CHECK(o.cls == NEW_SLAB);
+  s.check_all();
+  o = s.malloc(64 * MiB);  // which now serves the same request
+  CHECK(o.cls == HIT && o.ext_size == 64 * MiB);
+  s.finish();
+  ok(report(s));
+}
+
+// the switch off (unset, or a value out of range): the directed requests of
+// every kind log no fill; Sim::malloc checks the same in every other scenario
+void poison_off() {
+  Sim s;
+  CHECK(!s.poison, "this scenario needs GS_DEVMEM_POISON unset or out of range");
+  const size_t m = Sim::mark();
+  Outcome o = s.malloc(MiB);
+  CHECK(o.cls == PLAIN);
+  o = s.malloc(8 * GiB);
+  CHECK(o.cls == NEW_SLAB);
+  s.free(o.addr);
+  o = s.malloc(2 * GiB);
+  CHECK(o.cls == HIT);
+  s.set_room(0, 0);
+  o = s.malloc(64 * MiB);
+  CHECK(o.cls == HIT && o.relaxed);
+  s.set_room(0, 64 * GiB);
+  s.finish();
+  const auto v = Sim::since(m);
+  CHECK(v.fills.empty(), "%zu fill(s) with the switch off", v.fills.size());
+  ok(report(s));
+}
+
 // ---------------------------------------------------------------------- threads
 void threads() {
   static const size_t kSizes[] = {1 * MiB, 64 * MiB, 64 * MiB + 1, 100 * MiB, 512 * MiB, GiB - 1, 3 * GiB};
@@ -1305,6 +1463,10 @@ int main(int argc, char** argv) {
     devices();
   else if (s == "split_coalesce")
     split_coalesce();
+  else if (s == "poison")
+    poison_on();
+  else if (s == "poison_off")
+    poison_off();
   else if (s == "threads")
     threads();
   else if (s == "planner")

@@ -2,9 +2,9 @@
 pass planner (gs_rev_plan.h), on the CPU, against plain models.
 
 tests/devmem_harness.cpp is compiled together with the product's
-gs_devmem.cpp, unchanged, and defines the seven HIP entry points that file
-calls itself: a fake driver with three devices of 288 GB, a table of live
-allocations and a log of every call.  Nothing backs the addresses, so every
+gs_devmem.cpp, unchanged, and defines the eight HIP entry points that file
+calls itself (hipMemset among them, for GS_DEVMEM_POISON): a fake driver with
+three devices of 288 GB, a table of live allocations and a log of every call.  Nothing backs the addresses, so every
 path can be driven exactly, including the ones whose failure on a device is a
 fault: double frees, a device with no room, trimming.
 
@@ -98,10 +98,12 @@ def harness_tsan(_builds):
     return out
 
 
-def run(exe, scenario, cache=None):
-    env = {k: v for k, v in os.environ.items() if k not in ("GS_DEVMEM_CACHE", "GS_DEVMEM_LOG")}
+def run(exe, scenario, cache=None, poison=None):
+    env = {k: v for k, v in os.environ.items() if k not in ("GS_DEVMEM_CACHE", "GS_DEVMEM_LOG", "GS_DEVMEM_POISON")}
     if cache is not None:
         env["GS_DEVMEM_CACHE"] = cache
+    if poison is not None:
+        env["GS_DEVMEM_POISON"] = poison
     env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0"  # the cache and the fake driver live until exit
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"
     env["TSAN_OPTIONS"] = "halt_on_error=1"
@@ -111,6 +113,7 @@ def run(exe, scenario, cache=None):
     res = json.loads(lines[-1])
     assert p.returncode == 0 and res["ok"], f"{scenario}: exit {p.returncode}: {res}\n{p.stderr[-4000:]}"
     assert "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
+    res["stderr"] = p.stderr
     return res
 
 
@@ -149,6 +152,32 @@ def test_directed(harness, scenario):
 
 def test_bypass_with_the_cache_off(harness):
     run(harness, "bypass_off", cache="0")
+
+
+@pytest.mark.parametrize("byte", ["0xFF", "1", "0x7f"])
+def test_poison_fills_every_block_handed_out(harness, byte):
+    """GS_DEVMEM_POISON: plain, hit after a split, new slab and both fallbacks
+    are each followed by one fill of the whole block and one sync; a failed
+    fill is the request's error and leaves no block behind."""
+    res = run(harness, "poison", poison=byte)
+    assert res["stderr"].count("[devmem] poison 0x%02X\n" % int(byte, 0)) == 1, res["stderr"][-2000:]
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_random_sequence_poisoned(harness, seed):
+    """The same sequences with the switch on: every block handed out is
+    filled, whatever path served it."""
+    res = run(harness, f"random:{seed}", poison="0x01")
+    assert res["seen"].get("hit", 0) and res["seen"].get("new_slab", 0) and res["seen"].get("plain", 0)
+
+
+@pytest.mark.parametrize("value", [None, "0", "256", "-1", "0x100", "ff", "1x", ""])
+def test_poison_off_logs_no_fill(harness, value):
+    """Unset, or out of range, or not a number: no fill on any path, in the
+    directed requests and in a random run."""
+    for scenario in ("poison_off", "random:3", "no_room", "split_coalesce") if value is None else ("poison_off",):
+        res = run(harness, scenario, poison=value)
+        assert "[devmem] poison" not in res["stderr"]
 
 
 def test_threads_asan(harness):
